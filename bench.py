@@ -14,10 +14,12 @@ N > 1    : BASELINE.json configs[4]: n=25, groups up to size 6 (K_tot=245505), s
            Total work fixed => "scaling": "strong".  The line also carries the same configuration on ONE GPU
            (`single_gpu_value`) and N independent replicas of it (`replica_value`, no collective).
            --shard candidates|outputs keep the headline configuration and split it by allocation vector / by output.
-timing   : W warm-up steps, then `repeats` x K steps between barrier + synchronize; `repeats` is chosen so that the timed region
-           lasts >= 50 ms (K as passed; ms_per_step = elapsed / (repeats*K)).
+timing   : W warm-up steps, then exactly K timed steps queued right behind them, between two HIP events on the launch stream
+           (ms_per_step = elapsed / K; `repeats` is 1).
+outputs  : --dump-outputs DIR writes what the last timed step returned (V, grad V and status of every output) as DIR/<name>.npy
+           in float64, so that two builds can be compared output for output on the same seeded inputs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -34,7 +36,7 @@ sys.path.insert(0, ROOT)
 HEADLINE = (20, 5, 8)      # n, k_max, n_out  -- BASELINE.json configs[3]
 SHARDED = (25, 6, 1)       # BASELINE.json configs[4]
 HBM_PEAK = 8.0e12          # B/s, /opt/skills/guides/MI355X_MICROARCH.md
-MIN_TIMED_S = 0.05
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: larger arrays are written as a fixed, seeded sample of their entries
 
 
 def build_outputs(prob):
@@ -274,12 +276,11 @@ def sap_cpu_baseline(prob, gpu_max_variance, solve_seconds=10.0, setup_cap_s=14.
 
 
 class Stepper(object):
-    """W warm-up steps, then repeats x K timed steps; a hipGraph of `cycle` consecutive steps is replayed when that is possible
+    """W warm-up steps, then K timed steps; a hipGraph of `cycle` consecutive steps is replayed when that is possible
     (cycle <= K, so replays really happen inside the timed region) and everything else is launched eagerly -- the line says which"""
 
-    def __init__(self, torch, step, ring_len, steps, graph_steps, allow_graph, barrier, agree=None):
+    def __init__(self, torch, step, ring_len, steps, graph_steps, allow_graph, barrier):
         self.torch, self.step, self.barrier = torch, step, barrier
-        self.agree = agree if agree is not None else (lambda v: v)      # N > 1: max over the ranks, so all of them loop alike
         self.steps = steps
         self.cycle = 0
         self.graph = None
@@ -301,6 +302,8 @@ class Stepper(object):
                     with torch.cuda.graph(g, capture_error_mode="thread_local"):
                         for i in range(cycle):
                             step(i)
+                g.replay()                 # the first launch of a graph (upload) happens here, not inside a short timed region
+                torch.cuda.synchronize()
                 self.graph, self.cycle = g, cycle
             except Exception as err:   # keep the benchmark alive: eager launches measure the same work
                 sys.stderr.write("hipGraph capture failed (%s); falling back to eager launches\n" % err)
@@ -323,27 +326,19 @@ class Stepper(object):
         return "hipGraph replay of %d-step graphs (%d of %d steps), rest eager" % (self.cycle, replayed, self.steps)
 
     def timed(self, warmup):
-        """returns (seconds per step, repeats): the K-step block is repeated until the timed region is >= MIN_TIMED_S"""
+        """returns (seconds per step, repeats): exactly K steps between two HIP events on the launch stream, so repeats is
+        always 1.  The timed steps are queued right behind the warm-up steps with no synchronisation in between: the GPU goes
+        from the last warm-up step straight into the K timed ones, and the window holds them back to back rather than the host's
+        synchronisation latency (which dominates a short window timed with a host clock)"""
+        torch = self.torch
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        self.barrier()
         self.run(warmup)
-        self.barrier()
-        t0 = time.perf_counter()
+        e0.record()
         self.run(self.steps)
+        e1.record()
         self.barrier()
-        pilot = time.perf_counter() - t0
-        repeats = int(self.agree(max(1, int(np.ceil(MIN_TIMED_S / max(pilot, 1e-9))))))
-        while True:
-            self.barrier()
-            t0 = time.perf_counter()
-            for _ in range(repeats):
-                self.run(self.steps)
-            self.barrier()
-            elapsed = time.perf_counter() - t0
-            # the pilot block carries the synchronisation latency, so short blocks under-estimate the repeats: go again.  Every
-            # decision is taken on a value all ranks agree on (a different repeat count per rank would unbalance the collectives)
-            slowest = float(self.agree(elapsed))
-            if slowest >= MIN_TIMED_S or repeats >= 10 ** 6:
-                return elapsed / (repeats * self.steps), repeats
-            repeats = int(np.ceil(repeats * 1.25 * MIN_TIMED_S / max(slowest, 1e-9)))
+        return e0.elapsed_time(e1) * 1e-3 / self.steps, 1
 
 
 def chain_time(torch, fn, R=50, reps=20):
@@ -389,6 +384,19 @@ def eager_time(torch, fn, R=50, reps=7):
     return float(np.median(ts))
 
 
+def dump_outputs(dirname, arrays, suffix=""):
+    """--dump-outputs: every array as dirname/<name><suffix>.npy in float64; an array larger than DUMP_MAX_BYTES / len(arrays)
+    is replaced by a seeded sample of its flattened entries (the same indices in every run with the same arguments)"""
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_MAX_BYTES // (8 * len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > cap:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, cap, replace=False))
+            a, name = a.ravel()[idx], name + "_sample"
+        np.save(os.path.join(dirname, name + suffix + ".npy"), a)
+
+
 def launch_ranks(n, argv):
     """run this script as n ranks under torch.distributed.run (rendezvous on 127.0.0.1, a free port), stdout/stderr passed
     through; returns the launcher's exit code"""
@@ -425,6 +433,8 @@ def main():
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--kmax", type=int, default=None)
     ap.add_argument("--n-out", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write V, grad V and status of the last timed step to DIR/<name>.npy (float64; N > 1: one file per rank)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started plainly (`python bench.py --gpus N`): this process becomes the launcher -- it starts the N ranks as a CHILD
@@ -520,7 +530,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t[0])
 
-    stepper = Stepper(torch, step, len(ring), args.steps, args.graph_steps, graphable and not args.no_graph, barrier, agree)
+    stepper = Stepper(torch, step, len(ring), args.steps, args.graph_steps, graphable and not args.no_graph, barrier)
     sec_per_step, repeats = stepper.timed(args.warmup)
     if world > 1:
         t = torch.tensor([sec_per_step], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
@@ -528,6 +538,10 @@ def main():
         sec_per_step = float(t[0])
     assert bool((status == 0).all())
     assert bool(torch.isfinite(var).all())
+    if args.dump_outputs:
+        # before anything below reuses var / grad / status; the last timed step evaluated ring[(K - 1) % len(ring)]
+        dump_outputs(args.dump_outputs, {"variance": var.cpu().numpy(), "grad": grad.cpu().numpy(), "status": status.cpu().numpy()},
+                     "" if world == 1 else "_rank%d" % rank)
 
     extra = {}
     if world > 1 and not weak:
@@ -541,7 +555,7 @@ def main():
         assert float((var[0] / v_mine - 1).abs().max()) < 1e-10, "sharded evaluation disagrees with the single-GPU one"
         fv = torch.empty_like(v_full); fg = torch.empty_like(g_full); fs = torch.empty_like(st_full)
         full_step = lambda i: full.eval(ring[i % len(ring)], out=(fv, fg, fs))      # noqa: E731
-        rep_stepper = Stepper(torch, full_step, len(ring), args.steps, args.graph_steps, not args.no_graph, barrier, agree)
+        rep_stepper = Stepper(torch, full_step, len(ring), args.steps, args.graph_steps, not args.no_graph, barrier)
         rep_sec, _ = rep_stepper.timed(args.warmup)
         t = torch.tensor([rep_sec], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -637,7 +651,7 @@ def main():
                 bs = torch.empty((nc, n_out), dtype=torch.int32, device=dev)
                 brec = torch.empty((nc, n_out, plan.reclen), dtype=torch.float64, device=dev)
                 bstep = lambda i, rings=rings, bv=bv, bgr=bgr, bs=bs, brec=brec: sharded.eval(rings[i % 2], rec=brec, out=(bv, bgr, bs))   # noqa: E731
-                bst = Stepper(torch, bstep, 2, max(40, args.steps // nc), args.graph_steps, graphable and not args.no_graph, barrier, agree)
+                bst = Stepper(torch, bstep, 2, max(40, args.steps // nc), args.graph_steps, graphable and not args.no_graph, barrier)
                 sec, rpt = bst.timed(max(4, args.warmup // nc))
                 sec = float(agree(sec))
                 assert bool((bs == 0).all())

@@ -454,6 +454,24 @@ def gen_spg_bound(bluest, spgmod, n, kmax, fname, maxit):
     print(fname, "best f", best[0], "it", res["it"], "count", res["count"], "gpmax", res["gpmax"])
 
 
+def gen_ref_native(cm, fname):
+    """the reference's compiled module on the n = 10, k_max = 4 problem: the "as executed" evaluation (numpy psi@m + pinv + the
+    module's gradK_c, bench.py's reference-kind CPU baseline) and objectiveK_c for k = 1, 3, so that the restatement is checked
+    against them also where oracle/_ref is not built"""
+    n, kmax = 10, 4
+    prob = synth.problem(n, kmax, 1)
+    sap = orc.OracleSAP(prob["C"][0], kmax, prob["groups"], prob["costs"])
+    m = prob["m"][0]
+    V, grad, _ = sap.variance_GH_as_executed(m)
+    out = {"n": n, "kmax": kmax, "V_as_executed": V, "grad_as_executed": grad}
+    for k in (1, 3):
+        PHI = np.zeros(n * n)
+        cm.objectiveK_c(PHI, n, k, sap.sizes[k], m[sap.cumsizes[k - 1]:sap.cumsizes[k]], sap.groups[k - 1].ravel(), sap.invcovs[k - 1])
+        out["PHI_k%d" % k] = PHI
+    np.savez_compressed(os.path.join(OUT, fname), **out)
+    print(fname)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     cm, bluest, misc, spgmod = import_reference()
@@ -471,11 +489,15 @@ def main():
     gen_singular(bluest, "singular_phi_known_answer.npz")
     gen_spg_bound(bluest, spgmod, 12, 12, "spg_bound_n12_all.npz", maxit=400)
     gen_ns(bluest, "ns_paper_known_answer.npz")
+    gen_ref_native(cm, "ref_native_n10_k4.npz")
 
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--new-only":       # the fixtures added in round 3, leaving the others untouched
         cm_, bluest_, misc_, spgmod_ = import_reference()
         gen_ns(bluest_, "ns_paper_known_answer.npz")
+    elif len(sys.argv) > 1 and sys.argv[1] == "--ref-native-only":
+        cm_, bluest_, misc_, spgmod_ = import_reference()
+        gen_ref_native(cm_, "ref_native_n10_k4.npz")
     else:
         main()

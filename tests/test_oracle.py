@@ -258,16 +258,27 @@ def test_weighted_simplex_projection(oracle):
 
 
 def test_reference_native_module_agrees_with_restatement(oracle):
-    """oracle/_ref (the reference's own cmisc.cpp, compiled where /root/reference exists) vs the C restatement, and the
-    'as executed' evaluation used as bench.py's reference-kind CPU baseline.  Runs in a subprocess: oracle/_ref carries the
-    reference's -ffast-math, and importing it would switch the whole pytest process to flush-to-zero."""
+    """the reference's own compiled cmisc.cpp vs the C restatement, and the 'as executed' evaluation used as bench.py's
+    reference-kind CPU baseline: always against the module's recorded outputs (tests/golden/ref_native_n10_k4.npz,
+    oracle/gen_golden.py), and against the live module where oracle/_ref is built.  The live check runs in a subprocess:
+    oracle/_ref carries the reference's -ffast-math, and importing it would switch the whole pytest process to flush-to-zero."""
     import glob
     import os
     import subprocess
     import sys
+    G = golden("ref_native_n10_k4.npz")
+    n, kmax = int(G["n"]), int(G["kmax"])
+    prob = synth.problem(n, kmax, 1)
+    sap = oracle.OracleSAP(prob["C"][0], kmax, prob["groups"], prob["costs"])
+    m = prob["m"][0]
+    Vb, gb, _ = sap.variance_GH(m, nohess=True)
+    assert abs(G["V_as_executed"] / Vb - 1) < 1e-14 and np.abs(G["grad_as_executed"] - gb).max() / np.abs(gb).max() < 1e-14
+    for k in (1, 3):
+        ours = oracle.objectiveK(n, k, sap.sizes[k], m[sap.cumsizes[k - 1]:sap.cumsizes[k]], sap.groups[k - 1], sap.invcovs[k - 1])
+        assert np.abs(G["PHI_k%d" % k] - ours).max() / np.abs(ours).max() < 1e-15
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     if not glob.glob(os.path.join(root, "oracle", "_ref", "_cmisc_bluest*.so")):
-        pytest.skip("oracle/_ref not built (no reference tree here)")
+        return                                  # oracle/_ref is built only where the reference tree is present
     code = """
 import numpy as np
 from oracle import oracle
