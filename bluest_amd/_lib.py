@@ -84,6 +84,7 @@ SIGNATURES = {
     "bluest_price_capped": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "bluest_simplex_workspace_doubles": [c_i64, c_i64p],
     "bluest_simplex_project": [c_vp, c_vp, c_f64, c_f64, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "bluest_mfmc_search": [c_int, c_int, c_int, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
 
 

@@ -6,7 +6,8 @@ In scope here: given covariances and model costs -> model groups (cliques of the
 groups), their union over the outputs, group costs, one MOSAP on the GPU, `solver="spg"`, the reference's return dictionaries;
 `solve()` then samples the selected groups through the user's `sampler` / `evaluate` and forms the BLUE estimators.
 Out of scope (refused with BLUESTError): estimating covariances or costs by sampling, the SPD
-projection of incomplete covariances, saving / loading model graphs, MLMC / MFMC / plain-MC drivers.  An MPI communicator passed
+projection of incomplete covariances, saving / loading model graphs, the MLMC driver.  MFMC (setup_mfmc / solve_mfmc / compute_mfmc_data, the subset search on the
+GPU) and plain Monte Carlo (solve_mc) are in scope.  An MPI communicator passed
 as `comm` is honoured the way the reference uses it (optimiser and estimators on rank 0 + bcast, samples split over the ranks).
 
 Conventions kept from the reference (bluest/blue_models.py:43-56, :166-179): in a user covariance an infinite entry means "never
@@ -14,13 +15,18 @@ couple these two models", a zero entry means "uncorrelated" (such pairs are not 
 default); `get_covariance()` returns NaN where two models are not coupled.  Models that cannot be reached from model 0 through
 couplings are left out of every group (:312-322).
 """
+import ctypes
 from itertools import combinations
 
 import numpy as np
 
+from . import _lib, misc
 from .mosap import MOSAP
 from .host import in_host_section
 from .sap import BLUESTError
+
+BLUEST_MFMC_MAX_NEIGHBOURS = 30      # include/bluest_hip.h, Part 7
+BLUEST_MFMC_TOO_BIG = 2
 
 default_params = {"verbose": True, "comm": None, "remove_uncorrelated": True, "optimization_solver": "spg", "sample_batch_size": 1}
 
@@ -298,10 +304,165 @@ class BLUEProblem(object):
         Vs = self.comm.bcast(Vs, root=0)
         return mus, np.sqrt(Vs), out["cost"]
 
+    # ---- MFMC and plain Monte Carlo (bluest/blue_models.py:773-930) ------------------------------------------------------------
+    def _mfmc_inputs(self):
+        sigmas = [np.sqrt(np.diag(self.get_covariance(n))) for n in range(self.n_outputs)]
+        rhos = [self.get_correlation(n)[0, :] for n in range(self.n_outputs)]
+        return sigmas, rhos, self.get_costs()
+
+    def compute_mfmc_data(self, clique, samples):
+        """bluest/blue_models.py:773-795: the MFMC estimator of the group `clique` (model 0 first) with the given samples"""
+        sigmas, rhos, w = self._mfmc_inputs()
+        clique = list(clique)
+        if not all(cp.is_clique(clique) for cp in self._coupling):
+            raise ValueError("Group given is not a clique of the model graph!")
+        if clique[0] != 0:
+            raise ValueError("The high-fidelity model, model 0, should be the first in the given group!")
+        data = []
+        for n in range(self.n_outputs):
+            feasible, d = misc.compute_mfmc_data(sigmas[n][clique], rhos[n][clique], w[clique], samples)
+            if not feasible:
+                raise ValueError("Prescribed samples are not feasible for MFMC")
+            data.append(d)
+        return {"models": clique, "samples": samples, "errors": [d["error"] for d in data],
+                "total_cost": max(d["total_cost"] for d in data), "alphas": [d["alphas"] for d in data]}
+
+    @in_host_section
+    def setup_mfmc(self, budget=None, eps=None, continuous_relaxation=False, small_budget=False):
+        """bluest/blue_models.py:797-865: the best MFMC estimator over every clique through model 0 of the intersection of the
+        coupling graphs, searched on the GPU (bluest_mfmc_search).  Returns {"models", "samples", "errors", "total_cost",
+        "alphas"}; `models` is listed in the order the estimator uses (decreasing |rho|), and so are `samples` and `alphas`.
+        BLUESTError when the outputs order the selected models differently."""
+        if budget is None and eps is None:
+            raise ValueError("Need to specify either budget or RMSE tolerance")
+        elif budget is not None and eps is not None:
+            eps = None
+        if eps is not None and np.isscalar(eps): eps = [eps for n in range(self.n_outputs)]
+        if eps is None: eps = [None for n in range(self.n_outputs)]
+        sigmas, rhos, w = self._mfmc_inputs()
+        if self.verbose: print("Setting up optimal MFMC estimator...\n")
+        data = None
+        if self.mpiRank == 0:
+            data = self._mfmc_search(sigmas, rhos, w, budget, eps, continuous_relaxation, small_budget)
+            if self.verbose: print("Best MFMC estimator found. Coupled models:", data["models"], " Max error: ", max(data["errors"]),
+                                   " Cost: ", data["total_cost"], "\n")
+        return self.comm.bcast(data, root=0)
+
+    def _mfmc_search(self, sigmas, rhos, w, budget, eps, continuous_relaxation, small_budget):
+        linked = np.logical_and.reduce([cp.linked for cp in self._coupling])     # nx.intersection_all(self.G)
+        nbrs = [j for j in np.flatnonzero(linked[0]).tolist() if j != 0]
+        if len(nbrs) > BLUEST_MFMC_MAX_NEIGHBOURS:
+            raise BLUESTError("model 0 has %d neighbours: the MFMC search covers at most %d (2^%d subsets)"
+                              % (len(nbrs), BLUEST_MFMC_MAX_NEIGHBOURS, BLUEST_MFMC_MAX_NEIGHBOURS))
+        local = np.array([0] + nbrs, dtype=np.int64)
+        nb, n_out = len(nbrs), self.n_outputs
+        s = np.ascontiguousarray([sg[local] for sg in sigmas], dtype=np.float64)
+        rho = np.ascontiguousarray([r[local] for r in rhos], dtype=np.float64)
+        perm = np.ascontiguousarray([misc.mfmc_order(r) for r in rho], dtype=np.int32)
+        adj = np.array([sum(1 << (q - 1) for q in range(1, nb + 1) if q != p and linked[local[p], local[q]])
+                        for p in range(1, nb + 1)], dtype=np.uint32)
+        flags = (1 if budget is not None else 0) | (2 if continuous_relaxation else 0) | (4 if small_budget else 0)
+        eps2 = None if budget is not None else np.array([e**2 for e in eps], dtype=np.float64)
+        epsm2 = None if budget is not None else np.array([e**-2 for e in eps], dtype=np.float64)
+        wl = np.ascontiguousarray(w[local], dtype=np.float64)
+        mask, obj, status = ctypes.c_uint32(0), ctypes.c_double(0.0), ctypes.c_int32(0)
+        combo = np.zeros(n_out, dtype=np.uint32)
+        _lib.check(_lib.lib().bluest_mfmc_search(nb, n_out, flags, float(budget or 0.0), _lib.ptr(eps2), _lib.ptr(epsm2),
+                                                 _lib.ptr(wl), _lib.ptr(s), _lib.ptr(rho), _lib.ptr(perm), _lib.ptr(adj),
+                                                 ctypes.byref(mask), _lib.ptr(combo), ctypes.byref(obj), ctypes.byref(status),
+                                                 None))
+        if status.value == BLUEST_MFMC_TOO_BIG:
+            raise ValueError('Too many dimensions to brute-force it')
+        if status.value != 0:
+            raise BLUESTError("no group of models admits an MFMC estimator")
+        clique = [int(local[p]) for p in range(nb + 1) if p == 0 or (mask.value >> (p - 1)) & 1]
+        # every output's samples in its own |rho| order, then the element-wise maximum per model (blue_models.py:859)
+        per_output = []
+        for n in range(n_out):
+            cl = np.array(clique)
+            feasible, idx, m, variance, alphas = misc.mfmc_allocation(sigmas[n][cl], rhos[n][cl], w[cl], budget=budget, eps=eps[n])
+            assert feasible
+            if not continuous_relaxation:
+                if small_budget and budget is not None:
+                    m = misc.mfmc_low_budget_integer_solution(rhos[n][cl][idx], w[cl][idx], budget)
+                else:
+                    m = misc.mfmc_round_from_combo(m, combo[n])
+            per_output.append((cl[idx], m, variance, alphas))
+        models = [int(j) for j in per_output[0][0]]
+        if any(list(order) != models for order, _, _, _ in per_output[1:]):
+            # one MFMC estimator nests the samples of every output in ONE order; the reference would pair each output's samples
+            # and alphas with another output's order here, and report errors that do not describe what solve_mfmc computes
+            raise BLUESTError("the outputs order the selected models %s differently by |rho| (%s): MFMC needs one nesting order "
+                              "for all outputs" % (models, [[int(j) for j in order] for order, _, _, _ in per_output]))
+        samples = np.max(np.vstack([m for _, m, _, _ in per_output]), axis=0)
+        wm = w[models]
+        cost = samples @ wm
+        if budget is not None:          # adjust if budget bound (blue_models.py:850-854); the max takes care of the variance bound
+            samples = np.floor(samples - (max(cost - budget, 0) / (wm @ wm)) * wm).astype(np.int64)
+            samples[0] = max(samples[0], 1)
+            cost = samples @ wm
+        errs = [np.sqrt(variance(samples)) for _, _, variance, _ in per_output]
+        alphas = [al for _, _, _, al in per_output]
+        return {"models": models, "samples": samples, "errors": errs, "total_cost": cost, "alphas": alphas}
+
+    def solve_mfmc(self, budget=None, eps=None, mfmc_data=None, continuous_relaxation=False):
+        """bluest/blue_models.py:867-905: (estimates, their standard errors, total cost)"""
+        if budget is None and eps is None:
+            raise ValueError("Need to specify either budget or RMSE tolerance")
+        elif budget is not None and eps is not None:
+            eps = None
+        if mfmc_data is None:
+            mfmc_data = self.setup_mfmc(budget=budget, eps=eps, continuous_relaxation=continuous_relaxation)
+        best_group = list(mfmc_data["models"])
+        samples = np.round(mfmc_data["samples"]).astype(np.int64)
+        errs, tot_cost, alphas = mfmc_data["errors"], mfmc_data["total_cost"], mfmc_data["alphas"]
+        if self.verbose: print("\nSampling optimal MFMC estimator...\n")
+        L = len(best_group)
+        y = [[0 for i in range(L)] for n in range(self.n_outputs)]
+        y1 = [[0 for i in range(L - 1)] for n in range(self.n_outputs)]
+        for i in range(L):
+            N = samples[i]
+            if i > 0: N -= samples[i - 1]
+            sumse = self._group_sums(best_group[i:], N)
+            for n in range(self.n_outputs):
+                for j in range(i, L):
+                    y[n][j] += sumse[n][j - i]
+                    if j < L - 1: y1[n][j] += sumse[n][j - i + 1]
+        for n in range(self.n_outputs):
+            for i in range(L):
+                y[n][i] /= samples[i]
+                if i < L - 1: y1[n][i] /= samples[i]
+        mu = [y[n][0] + sum(alphas[n][i] * (y[n][i + 1] - y1[n][i]) for i in range(L - 1)) for n in range(self.n_outputs)]
+        return mu, errs, tot_cost
+
+    def solve_mc(self, budget=None, eps=None):
+        """bluest/blue_models.py:907-930: plain Monte Carlo on model 0"""
+        if budget is None and eps is None:
+            raise ValueError("Need to specify either budget or RMSE tolerance")
+        elif budget is not None and eps is not None:
+            eps = None
+        if eps is not None and np.isscalar(eps): eps = [eps for n in range(self.n_outputs)]
+        Vs = np.array([self.get_covariance(n)[0, 0] for n in range(self.n_outputs)])
+        cost = self.get_costs()[0]
+        if budget is not None:
+            N_MC = int(np.floor(budget / cost))
+            errs = np.sqrt(np.maximum(Vs, 0.0) / N_MC)
+            tot_cost = N_MC * cost
+        else:
+            N_MC = max(int(np.ceil(Vs[n] / eps[n]**2)) for n in range(self.n_outputs))
+            tot_cost = N_MC * cost
+            errs = np.sqrt(Vs / N_MC)
+        if self.verbose: print("Standard MC estimator ready. Max error: ", max(errs), "Cost: ", tot_cost)
+        if self.verbose: print("\nSampling standard MC estimator...\n")
+        sumse = self._group_sums([0], N_MC)
+        mu = [sumse[n][0] / N_MC for n in range(self.n_outputs)]
+        return mu, errs, tot_cost
+
     # ---- refused ----------------------------------------------------------------------------------------------------------------
     def _out_of_scope(self, *a, **k):
-        raise BLUESTError("outside this GPU build (SURVEY.md section 2): only setup_solver() / solve() with given covariances")
+        raise BLUESTError("outside this GPU build (SURVEY.md section 2): only setup_solver() / solve(), setup_mfmc() / solve_mfmc() "
+                          "and solve_mc() with given covariances")
 
-    setup_mlmc = solve_mlmc = setup_mfmc = solve_mfmc = setup_mc = solve_mc = _out_of_scope
+    setup_mlmc = solve_mlmc = setup_mc = _out_of_scope
     save_graph_data = load_graph_data = estimate_missing_covariances = project_covariances = estimate_costs = _out_of_scope
     complexity_test = variance_test = _out_of_scope

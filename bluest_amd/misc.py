@@ -119,3 +119,134 @@ def get_nnz_rows_cols(m, groups, cumsizes):
     ms = [m[cumsizes[k]:cumsizes[k + 1]] for k in range(K)]
     out = np.unique(np.concatenate([groups[k][abs(ms[k]) > 1.0e-6].flatten() for k in range(K)]))
     return out.reshape((len(out), 1)), out.reshape((1, len(out)))
+
+
+# ---- MFMC (bluest/misc.py:48-130, 141-175, 384-449): numpy mirrors for ONE model subset -------------------------------
+# O(L) each (the brute-force rounding O(2^L)); the search over subsets is bluest_mfmc_search (csrc/mfmc.hip).  Ties of |rho| and
+# of the allocation are ordered as a stable sort orders them (the reference's np.argsort is not stable on every machine).
+
+def mfmc_order(rhos):
+    """np.argsort(abs(rhos))[::-1] with ties by decreasing position (misc.py:57, 90)"""
+    idx = np.argsort(np.abs(rhos), kind="stable")[::-1]
+    assert idx[0] == 0
+    return idx
+
+
+def mfmc_integer_bounds(sol):
+    """get_feasible_integer_bounds(sol, len(sol)) of misc.py:141-167 for an allocation >= 1: every entry is rounded"""
+    idx = np.argsort(sol, kind="stable")
+    idx = np.array([i for i in idx if sol[i] > 1.0e-8], dtype=np.int64)
+    lb, ub = np.floor(sol).astype(int)[idx], np.ceil(sol).astype(int)[idx]
+    order = np.argsort(lb, kind="stable")[::-1]
+    return lb[order], ub[order], idx[order]
+
+
+def mfmc_round_from_combo(sol, combo):
+    """the integer point of combination `combo` of misc.py:390-393 (bit j: upper bound of the j-th bound entry)"""
+    lb, ub, idx = mfmc_integer_bounds(sol)
+    val = np.round(sol).astype(int)
+    bits = (int(combo) >> np.arange(len(idx))) & 1
+    val[idx] = np.where(bits == 1, ub, lb)
+    return val
+
+
+def _mfmc_sorted(sigmas, rhos, costs):
+    idx = mfmc_order(rhos)
+    s, w = sigmas[idx], costs[idx]
+    rho = np.concatenate([rhos[idx], [0]])
+    cost_ratio = w[:-1] / w[1:]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rho_ratio = (rho[:-2]**2 - rho[1:-1]**2) / (rho[1:-1]**2 - rho[2:]**2)
+    feasible = bool(np.all(cost_ratio > rho_ratio))
+    alphas = rho[1:-1] * s[0] / s[1:]
+    return idx, s, rho, w, alphas, feasible
+
+
+def _mfmc_variance(s, rho, alphas):
+    def variance(m):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return s[0]**2 / m[0] + sum((1 / m[:-1] - 1 / m[1:]) * (alphas**2 * s[1:]**2 - 2 * alphas * rho[1:-1] * s[0] * s[1:]))
+    return variance
+
+
+def mfmc_allocation(sigmas, rhos, costs, budget=None, eps=None):
+    """misc.py:90-107: (feasible, models in |rho| order, continuous allocation >= 1 in that order, variance callable, alphas)"""
+    if budget is None and eps is None:
+        raise ValueError("Need to specify either budget or RMSE tolerance")
+    elif budget is not None and eps is not None:
+        eps = None
+    idx, s, rho, w, alphas, feasible = _mfmc_sorted(sigmas, rhos, costs)
+    if not feasible:
+        return False, idx, None, None, alphas
+    r = np.sqrt(w[0] / w * (rho[:-1]**2 - rho[1:]**2) / (1 - rho[1]**2))
+    if budget is not None: m1 = budget / (w @ r)
+    else:                  m1 = eps**-2 * (w @ r) * (s[0]**2 / w[0]) * (1 - rho[1]**2)
+    m = np.maximum(np.concatenate([[m1], m1 * r[1:]]), 1)
+    return True, idx, m, _mfmc_variance(s, rho, alphas), alphas
+
+
+def mfmc_low_budget_integer_solution(rhos, costs, budget):
+    """misc.py:416-449 (Gruber et al. 2022, low-budget MFMC sample sizes)"""
+    if rhos.shape[0] == 1:
+        return np.array([np.floor(budget / costs[0])]).astype(np.int64)
+    rho = np.concatenate([rhos, [0]])
+    denom = rho[0] ** 2 - rho[1] ** 2
+    r = np.sqrt(costs[0] / costs * (rho[:-1] ** 2 - rho[1:] ** 2) / denom)
+    m1 = budget / (costs @ r)
+    m = np.concatenate([[m1], m1 * r[1:]])
+    if m[0] >= 1:
+        return np.floor(m).astype(np.int64)
+    m[0] = 1
+    m[1:] = mfmc_low_budget_integer_solution(rhos=rhos[1:], costs=costs[1:], budget=budget - costs[0])
+    return m.astype(np.int64)
+
+
+def _best_closest_integer_solution(sol, obj, constr):
+    """misc.py:384-413 with every candidate evaluated (argmin: the first minimum in combination order)"""
+    lb, ub, idx = mfmc_integer_bounds(sol)
+    LL = len(idx)
+    if LL > 24:
+        raise ValueError('Too many dimensions to brute-force it')
+    fvals = np.full(2**LL, np.inf)
+    for c in range(2**LL):
+        val = mfmc_round_from_combo(sol, c)
+        if constr(val): fvals[c] = obj(val)
+    c = int(np.argmin(fvals))
+    return mfmc_round_from_combo(sol, c), fvals[c]
+
+
+def attempt_mfmc_setup(sigmas, rhos, costs, budget=None, eps=None, continuous_relaxation=False, small_budget=False):
+    """misc.py:78-130: (feasible, {"samples", "error", "total_cost", "alphas", "variance"}), samples in |rho| order.
+    small_budget: the low-budget scheme is applied in |rho| order (the reference passes the unsorted arrays; the two agree
+    when model order follows |rho|)"""
+    if budget is not None and eps is not None:
+        eps = None
+    sigmas, rhos, costs = (np.asarray(a, dtype=np.float64) for a in (sigmas, rhos, costs))
+    if not all(np.isfinite(sigmas)): return False, None
+    feasible, idx, m, variance, alphas = mfmc_allocation(sigmas, rhos, costs, budget=budget, eps=eps)
+    if not feasible: return False, None
+    w = costs[idx]
+    if budget is not None:
+        constraint = lambda m: m @ w <= budget and m[0] >= 1 and all(m[:-1] <= m[1:])
+        obj = variance
+    else:
+        constraint = lambda m: variance(m) <= eps**2 and m[0] >= 1 and all(m[:-1] <= m[1:])
+        obj = lambda m: m @ w
+    if not continuous_relaxation:
+        if small_budget and budget is not None:
+            m = mfmc_low_budget_integer_solution(rhos[idx], w, budget)
+        else:
+            m, fval = _best_closest_integer_solution(m, obj, constraint)
+            if np.isinf(fval): return False, None
+    return True, {"samples": m, "error": np.sqrt(variance(m)), "total_cost": m @ w, "alphas": alphas, "variance": variance}
+
+
+def compute_mfmc_data(sigmas, rhos, costs, samples):
+    """misc.py:48-76: the MFMC estimator of given samples (listed in the models' order; returned in |rho| order)"""
+    sigmas, rhos, costs = (np.asarray(a, dtype=np.float64) for a in (sigmas, rhos, costs))
+    if not all(np.isfinite(sigmas)): return False, None
+    idx, s, rho, w, alphas, feasible = _mfmc_sorted(sigmas, rhos, costs)
+    if not feasible: return False, None
+    m = np.array(samples)[idx]
+    variance = _mfmc_variance(s, rho, alphas)(m)
+    return True, {"samples": m, "error": np.sqrt(variance), "total_cost": m @ w, "alphas": alphas, "variance": variance}

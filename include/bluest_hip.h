@@ -381,6 +381,29 @@ int bluest_price_capped(bluest_plan_t plan, const double *grad_dev, const double
                         int S, const int64_t *sup_dev, double *c_sup_dev, double *top_val_dev, int64_t *top_idx_dev, double *y0_dev,
                         const uint64_t *capmask_dev, const double *nu_dev, const double *master_out_dev, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Part 7 -- MFMC model-subset search (bluest/blue_models.py:795-865; allocation misc.py:78-130, rounding misc.py:384-413,
+ * low-budget scheme misc.py:416-449).  Local model index 0 is model 0, p = 1..nb the neighbours of model 0 in the intersection of
+ * the coupling graphs.  Host arrays: w (nb+1) costs; s, rho (n_out x (nb+1)) standard deviations and correlations with model 0;
+ * eps2 / epsm2 (n_out) eps**2 and eps**-2 (eps mode only); perm (n_out x (nb+1)) local indices by decreasing |rho|, model 0
+ * first; adj (nb) bit q-1 set when neighbours p and q are coupled.  Searches every clique through model 0 (2^nb bitmasks) and
+ * returns the reference's argmin (enumeration order on ties): best_mask (bit p-1 = neighbour p), best_combo (n_out: the index
+ * of the floor/ceil combination the rounding chose, bit j = ub of the j-th entry of get_feasible_integer_bounds; 0 when no
+ * rounding), best_obj, status.  Synchronous on `stream`; allocates and frees its own device memory.
+ * --------------------------------------------------------------------------------------------------------- */
+#define BLUEST_MFMC_MAX_NEIGHBOURS 30
+#define BLUEST_MFMC_MAX_ROUND      24   /* 'Too many dimensions to brute-force it' above this clique size */
+#define BLUEST_MFMC_MAX_OUTPUTS    64
+#define BLUEST_MFMC_BUDGET         1    /* flags */
+#define BLUEST_MFMC_CONTINUOUS     2
+#define BLUEST_MFMC_SMALL_BUDGET   4
+#define BLUEST_MFMC_OK             0    /* status */
+#define BLUEST_MFMC_NONE           1    /* no clique admits an MFMC estimator */
+#define BLUEST_MFMC_TOO_BIG        2    /* a feasible clique has more than BLUEST_MFMC_MAX_ROUND models to round */
+int bluest_mfmc_search(int nb, int n_out, int flags, double budget, const double *eps2, const double *epsm2, const double *w,
+                       const double *s, const double *rho, const int32_t *perm, const uint32_t *adj, uint32_t *best_mask,
+                       uint32_t *best_combo, double *best_obj, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
