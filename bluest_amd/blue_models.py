@@ -5,15 +5,23 @@ of `setup_solver()` / `solve()` of bluest/blue_models.py:448-576, on top of blue
 In scope here: given covariances and model costs -> model groups (cliques of the coupling graph up to size K, or the user's
 groups), their union over the outputs, group costs, one MOSAP on the GPU, `solver="spg"`, the reference's return dictionaries;
 `solve()` then samples the selected groups through the user's `sampler` / `evaluate` and forms the BLUE estimators.
-Out of scope (refused with BLUESTError): estimating covariances or costs by sampling, the SPD
-projection of incomplete covariances, saving / loading model graphs, the MLMC driver.  MFMC (setup_mfmc / solve_mfmc / compute_mfmc_data, the subset search on the
+The projection of the covariances onto the SPD matrices (`project_covariance(s)`, bluest/blue_models.py:348-433) is in scope:
+the eigendecompositions and the whole SPG solve run on the GPU (bluest_cov_project, one workgroup per output).  The
+constructor runs it only when asked (`skip_projection=False`; the default here is True, the reference's is False).
+Out of scope (refused with BLUESTError): estimating covariances or costs by sampling, saving /
+loading model graphs, the MLMC driver.  MFMC (setup_mfmc / solve_mfmc / compute_mfmc_data, the subset search on the
 GPU) and plain Monte Carlo (solve_mc) are in scope.  An MPI communicator passed
-as `comm` is honoured the way the reference uses it (optimiser and estimators on rank 0 + bcast, samples split over the ranks).
+as `comm` is honoured the way the reference uses it (optimiser, estimators and projection on rank 0 + bcast, samples split
+over the ranks).
 
 Conventions kept from the reference (bluest/blue_models.py:43-56, :166-179): in a user covariance an infinite entry means "never
 couple these two models", a zero entry means "uncorrelated" (such pairs are not coupled either when `remove_uncorrelated`, the
 default); `get_covariance()` returns NaN where two models are not coupled.  Models that cannot be reached from model 0 through
 couplings are left out of every group (:312-322).
+
+A quirk of the reference kept on purpose (:403-409): when the SPG projection ends with an objective above spg_params["eps"]
+and the problem is verbose, project_covariance() prints a warning and returns the error WITHOUT updating the covariance,
+unless bypass_error_check=True; a problem that is not verbose is always updated.
 """
 import ctypes
 from itertools import combinations
@@ -28,7 +36,39 @@ from .sap import BLUESTError
 BLUEST_MFMC_MAX_NEIGHBOURS = 30      # include/bluest_hip.h, Part 7
 BLUEST_MFMC_TOO_BIG = 2
 
-default_params = {"verbose": True, "comm": None, "remove_uncorrelated": True, "optimization_solver": "spg", "sample_batch_size": 1}
+BLUEST_COVPROJ_MAXIT, BLUEST_COVPROJ_MAXFEV, BLUEST_COVPROJ_NONFINITE = 1, 2, 3     # include/bluest_hip.h, Part 8
+BLUEST_MAX_MODELS = 64
+
+spg_default_params = {"maxit": 10000,                    # bluest/blue_models.py:10-17
+                      "max_fevals": 10000**2,
+                      "verbose": False,
+                      "spd_threshold": 5.0e-14,
+                      "eps": 1.0e-10,
+                      "lmbda_min": 10.**-30,
+                      "lmbda_max": 10.**30,
+                      "linesearch_history_length": 10,
+                      }
+
+default_params = {"verbose": True, "comm": None, "remove_uncorrelated": True, "optimization_solver": "spg", "sample_batch_size": 1,
+                  "skip_projection": True, "spg_params": spg_default_params}
+
+
+def cov_project(Cs, masks, spg_params):
+    """bluest_cov_project on a list of M x M covariances and 0/1 masks (1 = known entry): per output (X, f, gpmax, it, count,
+    info), the reference's spg() result fields, or the single clip (f = Frobenius error) where the mask is all ones"""
+    Cs = np.ascontiguousarray(np.array(Cs, dtype=np.float64))
+    masks = np.ascontiguousarray(np.array(masks, dtype=np.float64))
+    n_out, M = Cs.shape[0], Cs.shape[1]
+    X = np.empty_like(Cs)
+    f, gpmax = np.zeros(n_out), np.zeros(n_out)
+    it, count = np.zeros(n_out, dtype=np.int64), np.zeros(n_out, dtype=np.int64)
+    info = np.zeros(n_out, dtype=np.int32)
+    p = spg_params
+    _lib.check(_lib.lib().bluest_cov_project(M, n_out, _lib.ptr(Cs), _lib.ptr(masks), float(p["spd_threshold"]), float(p["eps"]),
+                                             float(p["lmbda_min"]), float(p["lmbda_max"]), int(p["maxit"]), int(p["max_fevals"]),
+                                             int(p["linesearch_history_length"]), _lib.ptr(X), _lib.ptr(f), _lib.ptr(gpmax),
+                                             _lib.ptr(it), _lib.ptr(count), _lib.ptr(info), None))
+    return [(X[n], float(f[n]), float(gpmax[n]), int(it[n]), int(count[n]), int(info[n])) for n in range(n_out)]
 
 
 class _SerialComm(object):
@@ -56,10 +96,15 @@ class _Coupling(object):
         never = np.isinf(C)
         self.cov = np.where(never, 0.0, C)
         self.linked = ~never
-        if remove_uncorrelated:
-            self.linked &= (self.cov != 0.0)
         np.fill_diagonal(self.linked, True)
         self.linked &= self.linked.T
+        self.check(remove_uncorrelated)
+
+    def check(self, remove_uncorrelated):
+        """drop the uncorrelated (zero) pairs when asked and find model 0's component (bluest/blue_models.py:305-322)"""
+        if remove_uncorrelated:
+            self.linked &= (self.cov != 0.0)
+            np.fill_diagonal(self.linked, True)
         # models reachable from model 0
         seen, frontier = {0}, [0]
         while frontier:
@@ -71,6 +116,10 @@ class _Coupling(object):
                         nxt.append(j)
             frontier = nxt
         self.component = sorted(seen)
+
+    def update(self, C_new):
+        """the projected covariance on the coupled pairs (bluest/blue_models.py:423-431); which pairs are coupled is unchanged"""
+        self.cov = np.where(self.linked, C_new, self.cov)
 
     def covariance(self):
         out = self.cov.copy()
@@ -100,6 +149,9 @@ class _Coupling(object):
 class BLUEProblem(object):
     def __init__(self, M, C=None, costs=None, mlmc_variances=None, datafile=None, n_outputs=1, **params):
         self.M, self.n_outputs = int(M), int(n_outputs)
+        spg_params = dict(spg_default_params)                  # merged as bluest/blue_models.py:64-67
+        spg_params.update(params.get("spg_params", {}))
+        params["spg_params"] = spg_params
         self.params = dict(default_params, **params)
         self.default_params = default_params
         comm = self.params["comm"]
@@ -123,7 +175,12 @@ class BLUEProblem(object):
         self._costs = np.array(costs, dtype=np.float64)
         if self._costs.shape != (self.M,):
             raise ValueError("costs must have one entry per model")
-        self._coupling = [_Coupling(c, self.params["remove_uncorrelated"]) for c in Cs]
+        project = not self.params["skip_projection"]
+        self._coupling = [_Coupling(c, self.params["remove_uncorrelated"] and not project) for c in Cs]
+        if project:                    # the reference's order (:94-101): project on the user's pattern, then drop uncorrelated pairs
+            self.project_covariances()
+            for cp in self._coupling:
+                cp.check(self.params["remove_uncorrelated"])
         self.SG = [cp.component for cp in self._coupling]
         for n, cp in enumerate(self._coupling):
             if len(cp.component) < self.M and self.warning:
@@ -458,11 +515,86 @@ class BLUEProblem(object):
         mu = [sumse[n][0] / N_MC for n in range(self.n_outputs)]
         return mu, errs, tot_cost
 
+    # ---- SPD projection of the covariances (bluest/blue_models.py:348-433) ----------------------------------------------------
+    def project_covariances(self, bypass_error_check=False):
+        """bluest/blue_models.py:348-350; every output in one launch, then each handled in order as project_covariance(n)"""
+        self._project(list(range(self.n_outputs)), bypass_error_check)
+
+    def project_covariance(self, n=0, bypass_error_check=False):
+        """bluest/blue_models.py:352-433: returns the projection error (the SPG objective, or ||C - C_new||_F when every entry
+        is known)"""
+        return self._project([n], bypass_error_check)[0]
+
+    @in_host_section
+    def _project(self, outputs, bypass_error_check):
+        spg_params = self.params["spg_params"]
+        if self.M > BLUEST_MAX_MODELS:
+            raise BLUESTError("the SPD projection covers at most %d models (this problem has %d)" % (BLUEST_MAX_MODELS, self.M))
+        Cs = [self.get_covariance(n) for n in outputs]
+        results = None
+        if self.mpiRank == 0:
+            results = cov_project([np.where(np.isnan(C), 0.0, C) for C in Cs], [(~np.isnan(C)).astype(np.float64) for C in Cs],
+                                  spg_params)
+        results = self.comm.bcast(results, root=0)
+        errs = []
+        for n, C, (X, f, gpmax, it, count, info) in zip(outputs, Cs, results):
+            finite = bool(np.isfinite(C).all())
+            if info == BLUEST_COVPROJ_NONFINITE:
+                raise BLUESTError("covariance %d has non-finite entries: it cannot be projected" % n)
+            if finite:
+                if info != 0:
+                    raise BLUESTError("covariance %d: the eigendecomposition did not converge" % n)
+                if self.verbose: print("Covariance projected to be symmetric positive definite, projection error: ", f)
+                C_new = X
+            else:
+                if self.verbose: print("Running Spectral Gradient Descent for Covariance projection...")
+                res = {"x": X.flatten(), "f": f, "gpmax": gpmax, "it": it, "count": count, "solver_info": info}
+                if spg_params["verbose"] and self.warning:
+                    self._print_spg_summary(res)
+                if info == 0:
+                    if self.verbose: print("Covariance projected, projection error: ", f)
+                    if f > spg_params["eps"] and self.verbose and not bypass_error_check:
+                        print("\n\n++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++")
+                        print("\nWARNING! Large covariance projection error. Model covariance may be singular. Consider removing one model.")
+                        print("Leaving covariances as they are. To bypass: run problem.project_variances(bypass_error_check=True) before setting up UQ solver.\n")
+                        print("++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++++\n\n")
+                        errs.append(f)
+                        continue
+                elif info in (BLUEST_COVPROJ_MAXIT, BLUEST_COVPROJ_MAXFEV):
+                    raise RuntimeError("Could not find good enough Covariance projection. Solver info:\n%s" % res)
+                else:
+                    raise BLUESTError("covariance %d: the eigendecomposition did not converge" % n)
+                C_new = X.copy()
+                sd = np.sqrt(np.diag(C_new))
+                rho_new = C_new / np.outer(sd, sd)
+                C_new[abs(rho_new) < 1.0e-7] = 0.0              # uncorrelated (the reference marks them inf: covariance 0)
+            self._coupling[n].update(C_new)
+            errs.append(f)
+        return errs
+
+    @staticmethod
+    def _print_spg_summary(res):
+        """the closing report of bluest/spg.py:105-132 (the per-iteration lines are not kept on the device)"""
+        print("\nSPECTRAL PROJECTED GRADIENT METHOD.\n")
+        print("Problem size:\t%d\n" % len(res["x"]))
+        print(" %d\t %e\t %e" % (res["it"], res["f"], res["gpmax"]))
+        print("\n")
+        print("Number of iterations               : %d\n" % res["it"])
+        print("Number of functional evaluations   : %d\n" % res["count"])
+        print("Objective function value           : %e\n" % res["f"])
+        print("Sup-norm of the projected gradient : %e\n" % res["gpmax"])
+        if res["solver_info"] == 0:
+            print("SPG: Optimal solution found.\n")
+        elif res["solver_info"] == 1:
+            print("WARNING! SPG: Maximum number of iterations reached.\n")
+        else:
+            print("WARNING! SPG: Maximum number of functional evaluations reached.\n")
+
     # ---- refused ----------------------------------------------------------------------------------------------------------------
     def _out_of_scope(self, *a, **k):
         raise BLUESTError("outside this GPU build (SURVEY.md section 2): only setup_solver() / solve(), setup_mfmc() / solve_mfmc() "
                           "and solve_mc() with given covariances")
 
     setup_mlmc = solve_mlmc = setup_mc = _out_of_scope
-    save_graph_data = load_graph_data = estimate_missing_covariances = project_covariances = estimate_costs = _out_of_scope
+    save_graph_data = load_graph_data = estimate_missing_covariances = estimate_costs = _out_of_scope
     complexity_test = variance_test = _out_of_scope

@@ -404,6 +404,31 @@ int bluest_mfmc_search(int nb, int n_out, int flags, double budget, const double
                        const double *s, const double *rho, const int32_t *perm, const uint32_t *adj, uint32_t *best_mask,
                        uint32_t *best_combo, double *best_obj, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Part 8 -- projection of the covariances onto the SPD matrices (bluest/blue_models.py:348-433, SPG of bluest/spg.py:39-132)
+ * Host arrays, n_out outputs of M x M row-major float64: C (NaN allowed where mask is 0), mask (1 = entry known, 0 = not
+ * coupled).  Per output, one workgroup of ONE launch:
+ *   - every mask entry nonzero: X = V max(l, spd_threshold) V^T with (l, V) = eigh of the lower triangle of C, f = ||C - X||_F,
+ *     gpmax = it = count = 0 (the reference's single clip);
+ *   - otherwise SPG on f(X) = 1/2 ||mask^2 o (X - C)||^2 with proj(X) = the clip of (X + X^T)/2, started at proj(mask o C),
+ *     stopping when max|proj(x - g) - x| <= eps, after maxit iterations or max_fevals evaluations; nonmonotone line search over
+ *     the last hlength values, Barzilai-Borwein step clamped to [lmbda_min, lmbda_max].  X, f, gpmax, it, count as spg() returns
+ *     them.
+ * info: BLUEST_COVPROJ_* below (the reference's solver_info 0 / 1 / 2, then this build's own).  M outside 1..BLUEST_MAX_MODELS,
+ * n_out outside 1..BLUEST_COVPROJ_MAX_OUTPUTS or hlength outside 1..BLUEST_COVPROJ_MAX_HISTORY return BLUEST_ERR_ARG.
+ * Synchronous on `stream`; allocates and frees its own device memory.
+ * --------------------------------------------------------------------------------------------------------- */
+#define BLUEST_COVPROJ_OK          0   /* converged (SPG) / clipped (all entries known) */
+#define BLUEST_COVPROJ_MAXIT       1   /* maxit iterations reached */
+#define BLUEST_COVPROJ_MAXFEV      2   /* evaluation budget spent (X = the last accepted point) */
+#define BLUEST_COVPROJ_NONFINITE   3   /* a known entry of C, or an entry of mask, is not finite: X = C, nothing computed */
+#define BLUEST_COVPROJ_NOEIG       4   /* a Jacobi eigendecomposition did not converge in its sweep budget */
+#define BLUEST_COVPROJ_MAX_OUTPUTS 1024
+#define BLUEST_COVPROJ_MAX_HISTORY 64
+int bluest_cov_project(int M, int n_out, const double *C, const double *mask, double spd_threshold, double eps, double lmbda_min,
+                       double lmbda_max, int64_t maxit, int64_t max_fevals, int hlength, double *X_out, double *f_out,
+                       double *gpmax_out, int64_t *it_out, int64_t *count_out, int32_t *info_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
