@@ -10,7 +10,6 @@ Everything numeric runs in hand-written kernels; the host only moves a few KB pe
 multipliers, 1024 pricing candidates) and decides which groups enter.  torch is used for buffers and the stream only.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -217,7 +216,7 @@ def colgen_solve(plan, costs, s, B, x0=None, prm=None, log=None, caps=None):
         _t_ma0 = _time.perf_counter()
         # a single output on all groups: the fused solve + gradient kernel of the evaluation applies the update itself (two launches
         # per step instead of three, no gradient array; the same iterates bit for bit)
-        fused_ma = sharded is None and n_out == 1 and bool(getattr(plan, "identity", False)) and os.environ.get("BLUEST_MA_FUSED", "1") != "0"
+        fused_ma = sharded is None and n_out == 1 and bool(getattr(plan, "identity", False))
         for _ in range(ma_its):
             if fused_ma:
                 check(lib.bluest_plan_eval_ma(plan._h, m_d.data_ptr(), var.data_ptr(), status.data_ptr(), s_d.data_ptr(), cc.data_ptr(), x_d.data_ptr(), st))
@@ -335,8 +334,6 @@ def colgen_solve(plan, costs, s, B, x0=None, prm=None, log=None, caps=None):
                     info["master_evals"] += int(out[5])
                     info["full_evals"] += 1
                     info["master_solves"] = info.get("master_solves", 0) + int(out[6])
-                    if out[10:16].any():                              # experiment build (-DMASTER_TIMING): per-phase microseconds
-                        info["master_phase_us"] = [a + b for a, b in zip(info.get("master_phase_us", [0.0] * 8), out[8:16])]
                     if int(out[7]) == 2 or not np.isfinite(out[0]):
                         return None, "master start not evaluable"
                     xs, mu = h["xs"][:S].copy(), h["mu"].copy()

@@ -26,9 +26,6 @@
 // MF_AUTO_BYTES (the evaluation is then bound by bytes, profiles/r04_matfree_ab.txt).
 #include "plan.hpp"
 
-#ifndef MF_ABLATE          // experiment builds only (timing; the ablated builds compute wrong numbers): 1 no LDS adds, 2 no run sums,
-#define MF_ABLATE 0        // 3 no inverse (the factor's entries are scattered), 4 tiles load their inputs and do nothing else
-#endif
 #define MF_KMAX 8
 #define MF_TILE_WAVES 15                       // tile wavefronts of k_solve_grad_mf (+ the solving one)
 static const int64_t MF_AUTO_BYTES = 64ll << 20;
@@ -127,9 +124,7 @@ __device__ __forceinline__ void mf_phi_tile(int n_valid, uint64_t pk, double mg,
     int idx[K];
     double a[mf_ke(K)], r[K];
     mf_load_block<K>(pk, valid, Cs, N, idx, a);
-    if (MF_ABLATE == 4) { if (a[0] == 1.2345 && mg == 5.4321) acc[idx[0]] = 1.0; return; }
-    if (MF_ABLATE != 3) (void)mf_chol<K>(a, r);
-    else { _Pragma("unroll") for (int i = 0; i < K; i++) r[i] = 1.0; }
+    (void)mf_chol<K>(a, r);
     // M = L^-1 (lower) in place of L: M_jj = r_j, M_ij = -r_i sum_{p=j}^{i-1} L_ip M_pj  (column by column, rows top down)
     double M[mf_ke(K)];
 #pragma unroll
@@ -179,12 +174,10 @@ __device__ __forceinline__ void mf_phi_tile(int n_valid, uint64_t pk, double mg,
 #pragma unroll
             for (int q = i; q < K; q++) sij = fma(M[q * (q + 1) / 2 + i], M[q * (q + 1) / 2 + j], sij);
             double v = mg * sij;
-            if (MF_ABLATE != 2) {
-                v = fma(dpp_shr<0x111>(v), nf[0], v);
-                v = fma(dpp_shr<0x112>(v), nf[1], v);
-                v = fma(dpp_shr<0x114>(v), nf[2], v);
-                v = fma(dpp_shr<0x118>(v), nf[3], v);
-            }
+            v = fma(dpp_shr<0x111>(v), nf[0], v);
+            v = fma(dpp_shr<0x112>(v), nf[1], v);
+            v = fma(dpp_shr<0x114>(v), nf[2], v);
+            v = fma(dpp_shr<0x118>(v), nf[3], v);
             tot[i * (i + 1) / 2 + j] = v;
         }
         // max |m_g| over the groups containing model idx_i: same runs (|m| >= 0, lanes outside the row read 0)
@@ -195,7 +188,6 @@ __device__ __forceinline__ void mf_phi_tile(int n_valid, uint64_t pk, double mg,
         mx = fmax(mx, dpp_shr<0x118>(mx) * nf[3]);
         mxs[i] = mx;
     }
-    if (MF_ABLATE == 1) { double z = 0.0; _Pragma("unroll") for (int e = 0; e < mf_ke(K); e++) z += tot[e]; if (z == 1.2345) acc[0] = z; return; }
 #pragma unroll
     for (int i = 0; i < K; i++) {
         if (tails[i]) {
@@ -555,8 +547,6 @@ int mf_finalize(bluest_plan_t plan)
     int64_t most = 0;
     for (int o = 0; o < n_out; o++) most = std::max<int64_t>(most, S->tile_begin[o + 1] - S->tile_begin[o]);
     S->wgs = (int)std::max<int64_t>(1, std::min<int64_t>((cus + n_out - 1) / n_out, (most + S->nw - 1) / S->nw));
-    const char *wenv = getenv("BLUEST_MATFREE_WGS");
-    if (wenv && atoi(wenv) >= 1) S->wgs = atoi(wenv);
     // mappings (identity plans need none)
     std::vector<int32_t> map;
     if (!plan->identity) {

@@ -11,39 +11,22 @@
 // bluest/cmisc.cpp:74-97 (bluest/sap.py:387-456); there is no reference code to follow.
 #include "plan.hpp"     // brings solve.hpp: readlane_f64, wave_lds_sync
 
-#ifdef MASTER_TIMING      // experiment build only: per-phase wall-clock (100 MHz counter) of thread 0, accumulated in L.scal[240..248] (as
-                          // 64-bit integers; slot 8 = the last stamp) and returned in out[8..15] -- the record's damping / multiplier
-                          // slots are overwritten, nothing on the host reads them.  Phases: 0 load, 1 Phi assembly, 2 elimination of the
-                          // evaluations, 3 active set + derivatives, 4 free set / step formation / bookkeeping, 5 Hessian, 6 elimination of
-                          // the Newton system, 7 K + the small KKT system
-#define TSTAMP(k) do { __syncthreads(); if (threadIdx.x == 0) { long long *tq_ = reinterpret_cast<long long *>(L.scal + 240); const long long t_ = wall_clock64(); tq_[k] += t_ - tq_[12]; tq_[12] = t_; } } while (0)
-#else
-#define TSTAMP(k)
-#endif
 #define MASTER_THREADS 512
 #define MASTER_SMAX 64
-#ifndef MASTER_PACT
 #define MASTER_PACT 8      // candidate outputs (within act_tol of the maximum) of one step of the master.  6 until round 4: with 7 or 8
                            // outputs tied at the optimum (headline shape, other covariance seeds) the step cannot equalise them and the
                            // master ends at a KKT measure of 3e-5, certified gap 1.4e-5 -- profiles/r04_seed_sweep.txt.  The scal[] blocks
                            // SQ / SQT / SMU (8 slots each) and the 16-lane KKT system (8 + MASTER_MCAP + 2 rows) are sized for 8
-#endif
 #define MASTER_MCAP 4      // sample caps (max_model_samples rows) that can be in the step as equality rows at once
 #define MASTER_NE (MASTER_PACT + MASTER_MCAP + 1)      // columns of E: active outputs, active caps, the simplex row
 #define MASTER_OUT 16      // doubles in front of r[] in the result record
-#ifndef MASTER_DAMP_DOWN
 #define MASTER_DAMP_DOWN 0.3   // damping after a step whose decrease was more than half of the predicted one.  x0.1 (until round 4) made
                                // the masters oscillate -- accepted, x0.1, the next step too long and rejected, x10, accepted ... : 45 of 116
-                               // factorisations of a headline solve ended in a rejected step; profiles/r04_damp_ab.txt (tools/damp_ab.sh)
-#endif
-#ifndef MASTER_DAMP_HOLD
-#define MASTER_DAMP_HOLD 0     // 1: a step that was accepted only after a rejection keeps its damping for the next iteration (A/B switch: with
-                               // x4 after a rejection it is 0-3 % faster on the synthetic shapes and takes the ill-conditioned Navier-Stokes problem's
-                               // certified gap to 6e-5 under perturbed parameters -- profiles/r04_damp_ab.txt; not shipped)
-#endif
-#ifndef MASTER_DAMP_UP
+                               // factorisations of a headline solve ended in a rejected step; profiles/r04_damp_ab.txt.  Also measured there
+                               // and not shipped: a step accepted only after a rejection keeping its damping for the next iteration (with x4
+                               // after a rejection 0-3 % faster on the synthetic shapes, but the ill-conditioned Navier-Stokes problem's
+                               // certified gap went to 6e-5 under perturbed parameters)
 #define MASTER_DAMP_UP 10.0    // ... after a rejected step
-#endif
 #define MASTER_STATIC_LDS 2048   // room kept for the kernel's static LDS (the small KKT system: 1.5 KB) next to the dynamic part
 
 struct MasterArgs {
@@ -390,9 +373,6 @@ __device__ void master_eval(const MasterArgs &A, MasterLds &L, const double *xv,
         }
     for (int j = tid; j < S; j += MASTER_THREADS) L.mvec[j] = (1.0 - A.eps_bg) * L.cc[j] * xv[j];
     __syncthreads();
-#ifdef MASTER_TIMING_FINE
-    TSTAMP(8);
-#endif
     const int sub = tid & 3;
     for (int d0 = 0; d0 < ND; d0 += MASTER_THREADS / 4) {
         const int d = d0 + (tid >> 2);
@@ -435,7 +415,6 @@ __device__ void master_eval(const MasterArgs &A, MasterLds &L, const double *xv,
         }
     }
     __syncthreads();
-    TSTAMP(1);
     for (int o = wave; o < n_out; o += nw) {
         double *P = L.PHI + (size_t)o * PHS;
         double v00;
@@ -448,7 +427,6 @@ __device__ void master_eval(const MasterArgs &A, MasterLds &L, const double *xv,
         if (lane == 0) rout[o] = (v00 > 0.0 && isfinite(v00)) ? v00 / A.s[o] : INFINITY;
     }
     __syncthreads();
-    TSTAMP(2);
 }
 
 // Hessian of the Lagrangian in reciprocal form + damping into M (free x free, compressed), E columns appended -- all threads
@@ -578,7 +556,6 @@ __device__ void master_factor_all(const MasterArgs &A, MasterLds &L, int tid)
     double mypiv = 1.0;
     if (wave == 0) factor_publish(L, am[0], 0, nf, lane);
     const bool ok = FactorStep<0>::run(L, am, ae, mypiv, nf, ne, wave, lane);
-    TSTAMP(6);
     __syncthreads();
     if (!ok) { if (tid == 0) L.istate[IS_OK] = 0; __syncthreads(); return; }
     const double dinv = row ? rcp_f64(mypiv) : 0.0;
@@ -827,9 +804,6 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
     for (int t = tid; t < n_out * L.PHS; t += MASTER_THREADS) L.PHI[t] = 0.0;      // pads of the reversed layout stay zero
     if (tid < 64) { L.capmodel[tid] = tid < A.ncap ? A.cap_model[tid] : 0; L.capb[tid] = tid < A.ncap ? A.cap_b[tid] : 0.0; L.nu[tid] = 0.0; L.capslack[tid] = 0.0; }
     __syncthreads();
-#ifdef MASTER_TIMING
-    if (tid == 0) reinterpret_cast<long long *>(L.scal + 240)[12] = wall_clock64();
-#endif
     for (int t = tid; t < S * KM; t += MASTER_THREADS) {
         const int j = t / KM, l = t % KM;
         if (l < L.kk[j]) L.pos[j * N + L.idx[t]] = (signed char)l;
@@ -903,7 +877,6 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
         L.scal[SC_DAMP] = damp0; L.istate[IS_STATUS] = 0; L.scal[SC_MBEST] = INFINITY;
     }
     __syncthreads();
-    TSTAMP(0);                                          // 0: load
     master_eval<NT>(A, L, L.x, L.r, tid);
     if (tid == 0) {
         L.istate[IS_EVALS] = 1;
@@ -985,9 +958,6 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
             }
         }
         __syncthreads();
-#ifdef MASTER_TIMING_FINE
-        TSTAMP(9);
-#endif
         for (int t = tid; t < nact0 * S * KM; t += MASTER_THREADS) {
             const int l = t % KM, j = (t / KM) % S, a = t / (KM * S);
             const int o = L.act[a + MASTER_PACT], k = L.kk[j];
@@ -1003,9 +973,6 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
             L.AAC[t] = acc;
         }
         __syncthreads();
-#ifdef MASTER_TIMING_FINE
-        TSTAMP(10);
-#endif
         for (int t = tid; t < S * nact0; t += MASTER_THREADS) {
             const int a = t % nact0, j = t / nact0;
             const int o = L.act[a + MASTER_PACT], k = L.kk[j];
@@ -1022,7 +989,6 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
             L.scal[SC_QMAX] = qm;
         }
         __syncthreads();
-        TSTAMP(3);                                      // 3: active set + derivatives
         if (wave == 0) {   // reduced costs with the curvature weights -> free set
             double part = 0.0;
             for (int j = lane; j < S; j += 64) {
@@ -1053,24 +1019,15 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
             if (tid == 0) L.istate[IS_NACT] = L.istate[IS_NACT0];
             if (tid < MASTER_PACT) L.act[tid] = L.act[tid + MASTER_PACT];
             __syncthreads();
-            TSTAMP(4);                                  // 4: free set, KKT bookkeeping, step formation
             master_build_system(A, L, tid, attempt > 0);
-            TSTAMP(5);                                  // 5: Hessian / system assembly
             master_factor_all(A, L, tid);
-#ifdef MASTER_TIMING_FINE
-            TSTAMP(11);
-#endif
             if (wave == 0) {
                 if (L.istate[IS_OK]) master_small_solve(A, L, lane, false, L.d);
                 if (lane == 0) L.istate[IS_SOLVES] += 1;
             }
             __syncthreads();
-            TSTAMP(7);                                  // 7: K + small system
             if (!L.istate[IS_OK]) {              // M not positive definite (or singular small system): more damping
                 __syncthreads();
-#ifdef MASTER_COUNTS
-                if (tid == 0) L.scal[200] += 1.0;
-#endif
                 if (tid == 0) L.scal[SC_DAMP] *= 10.0;
                 __syncthreads();
                 if (L.scal[SC_DAMP] > 1.0e12) break;
@@ -1133,9 +1090,6 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
             if (attempt == 0) pred0 = pred;
             if (pred < -0.5 * F) {               // the model promises more than half of a positive objective: shorter step
                 __syncthreads();
-#ifdef MASTER_COUNTS
-                if (tid == 0) L.scal[201] += 1.0;
-#endif
                 if (tid == 0) L.scal[SC_DAMP] *= 10.0;
                 __syncthreads();
                 if (L.scal[SC_DAMP] > 1.0e12) break;
@@ -1154,7 +1108,6 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
                 if (A.ncap > 0) { wave_lds_sync(); master_cap_feasible(A, L, lane); }
             }
             __syncthreads();
-            TSTAMP(4);
             master_eval<NT>(A, L, L.xt, L.rt, tid);
             // acceptance; near a tie of several outputs second-order errors split the tie and the exact max rejects a good SQP
             // step (the Maratos effect): one second-order correction -- the minimum-norm (in M) step c that re-equalises the
@@ -1173,7 +1126,7 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
                     const bool noise = pred > -1.0e-11 * F && fmax(L.scal[SC_KKT], L.scal[SC_SPREAD]) <= 1.0e-4 && L.scal[SC_DAMP] <= 1.0e-2;      // (a tiny step of a heavily damped system is not noise)
                     if (isfinite(Ft) && (actual <= 1.0e-4 * fmin(pred, 0.0) + 1.0e-15 * F || (noise && actual <= 1.0e-11 * F))) {
                         const double ratio = (pred < 0.0 && !noise) ? actual / pred : 1.0;      // a step taken on trust counts as a good one
-                        if (ratio > 0.5 && (attempt == 0 || !MASTER_DAMP_HOLD)) L.scal[SC_DAMP] = fmax(L.scal[SC_DAMP] * MASTER_DAMP_DOWN, 1.0e-14);
+                        if (ratio > 0.5) L.scal[SC_DAMP] = fmax(L.scal[SC_DAMP] * MASTER_DAMP_DOWN, 1.0e-14);
                         else if (ratio < 0.1) L.scal[SC_DAMP] *= 10.0;
                         L.istate[IS_ACCEPT] = 1;
                         L.scal[SC_FT] = Ft;
@@ -1181,15 +1134,8 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
                     } else if (pass == 0 && isfinite(Ft) && L.istate[IS_NALIVE] > 1) {
                         for (int a = 0; a < L.istate[IS_NACT0]; a++) L.scal[SQT + a] = -1.0 / L.rt[L.act[a + MASTER_PACT]];
                         L.istate[IS_OK] = 1;
-#ifdef MASTER_COUNTS
-                        L.scal[202] += 1.0;
-#endif
                     } else {
                         L.scal[SC_DAMP] *= MASTER_DAMP_UP;
-#ifdef MASTER_COUNTS
-                        L.scal[203] += 1.0; if (!isfinite(Ft)) L.scal[204] += 1.0;
-                        if (isfinite(Ft) && pred < 0.0) { const double rr = actual / pred; if (rr > -1.0) L.scal[205] += 1.0; }
-#endif
                     }
                 }
                 __syncthreads();
@@ -1264,17 +1210,6 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
         A.out[0] = L.scal[SC_F]; A.out[1] = L.scal[SC_LAM]; A.out[2] = L.scal[SC_KKT]; A.out[3] = L.scal[SC_SPREAD];
         A.out[4] = L.istate[IS_IT]; A.out[5] = L.istate[IS_EVALS]; A.out[6] = L.istate[IS_SOLVES]; A.out[7] = L.istate[IS_STATUS];
         A.out[8] = L.scal[SC_DAMP]; A.out[9] = L.scal[SC_LAMX];
-#ifdef MASTER_COUNTS
-        printf("COUNTS S %d it %d solves %d evals %d | notPD %g modelTooBig %g soc %g rejected %g (inf %g, mild %g) status %d\n", S, L.istate[IS_IT], L.istate[IS_SOLVES], L.istate[IS_EVALS],
-               L.scal[200], L.scal[201], L.scal[202], L.scal[203], L.scal[204], L.scal[205], L.istate[IS_STATUS]);
-#endif
-#ifdef MASTER_TIMING
-        for (int k = 0; k < 8; k++) A.out[8 + k] = (double)reinterpret_cast<long long *>(L.scal + 240)[k] * 0.01;      // microseconds
-#ifdef MASTER_TIMING_FINE
-        printf("FINE %lld %lld %lld %lld\n", reinterpret_cast<long long *>(L.scal + 240)[8], reinterpret_cast<long long *>(L.scal + 240)[9],
-               reinterpret_cast<long long *>(L.scal + 240)[10], reinterpret_cast<long long *>(L.scal + 240)[11]);
-#endif
-#endif
     }
 }
 

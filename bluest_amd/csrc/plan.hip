@@ -19,47 +19,11 @@
 //                tile wavefronts streaming -- non-temporal loads -- while it factorises; tiles per workgroup chosen per plan
 //                so that the workgroups cover every compute unit).
 //   * What bounds a step after round 3: the two copies of the inverses (Phi layout + tiles) evict each other from the L2s; see
-//                DESIGN.md section 4 and profiles/r03_phi_tiles_negative_result.txt (k_phi_tiles below is the single-copy pass).
+//                DESIGN.md section 4 and profiles/r03_phi_tiles_negative_result.txt (a single-copy pass measured slower).
 // No CPU fallback exists in this library.
 
 #include "common.hpp"
 
-#ifndef BLUEST_ABLATE      // experiment builds only (-DBLUEST_ABLATE=n, tools/ablate.sh): parts of the evaluation kernels switched off
-#define BLUEST_ABLATE 0    // for timing: 1 no fold, 2 no elimination, 3 no tile stream, 5 empty k_solve_grad, 6 empty Phi pass, 7 no gradient
-                           // store, 8 Phi pass stores its partials elsewhere, 9 Phi pass only stores, 10 / 11 k_phi_tiles: products only / no tile loads, 12 Phi pass without the gather of m
-#endif
-#ifdef BLUEST_PHASE_TIMING   // experiment builds only (tools/phase_timing.py): 100 MHz timestamps of one workgroup's phases
-__device__ long long g_phase[3][12];
-#define PHASE(i) do { if (threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x / 2 || blockIdx.x == gridDim.x - 1)) \
-        g_phase[blockIdx.x == 0 ? 0 : (blockIdx.x == gridDim.x - 1 ? 2 : 1)][i] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-extern "C" int bluest_debug_phase_times(long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), sizeof(long long) * 36) == hipSuccess ? 0 : 1; }
-// the same for the first TILE wavefront (thread 64) of the three sampled workgroups
-__device__ long long g_phase_tile[3][8];
-#define PHASE_TILE(i) do { if (threadIdx.x == 64 && (blockIdx.x == 0 || blockIdx.x == gridDim.x / 2 || blockIdx.x == gridDim.x - 1)) \
-        g_phase_tile[blockIdx.x == 0 ? 0 : (blockIdx.x == gridDim.x - 1 ? 2 : 1)][i] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-extern "C" int bluest_debug_phase_times_tile(long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase_tile), sizeof(long long) * 24) == hipSuccess ? 0 : 1; }
-// kernel spans in a chain of evaluations: [step % 16][kernel][begin, end] (min / max over a sample of workgroups)
-__device__ unsigned long long g_span[16][2][2];
-__device__ int g_step;
-#define SPAN_SAMPLED() (threadIdx.x == 0 && blockIdx.y == 0 && (blockIdx.x < 8 || blockIdx.x + 8 >= gridDim.x || (blockIdx.x & 31) == 0))
-#define SPAN_BEGIN(kid) const int span_step_ = g_step & 15; \
-    do { if (SPAN_SAMPLED()) atomicMin(&g_span[span_step_][kid][0], (unsigned long long)wall_clock64()); } while (0)
-#define SPAN_END(kid, bump) do { if (SPAN_SAMPLED()) atomicMax(&g_span[span_step_][kid][1], (unsigned long long)wall_clock64()); \
-        if (bump && threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0) g_step = g_step + 1; } while (0)
-extern "C" int bluest_debug_span_reset(void)
-{
-    unsigned long long h[16][2][2];
-    for (int i = 0; i < 16; i++) for (int k = 0; k < 2; k++) { h[i][k][0] = ~0ull; h[i][k][1] = 0ull; }
-    int z = 0;
-    return (hipMemcpyToSymbol(HIP_SYMBOL(g_span), h, sizeof(h)) == hipSuccess && hipMemcpyToSymbol(HIP_SYMBOL(g_step), &z, sizeof(z)) == hipSuccess) ? 0 : 1;
-}
-extern "C" int bluest_debug_span_read(unsigned long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_span), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : 1; }
-#else
-#define PHASE(i)
-#define PHASE_TILE(i)
-#define SPAN_BEGIN(kid)
-#define SPAN_END(kid, bump)
-#endif
 static int g_debug_timing = getenv("BLUEST_DEBUG_TIMING") ? 1 : 0;   // stderr phase times of the set-up entry points
 struct PhaseTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -73,7 +37,6 @@ struct PhaseTimer {
         t0 = t1;
     }
 };
-static int g_debug_solve = getenv("BLUEST_DEBUG_SOLVE") ? atoi(getenv("BLUEST_DEBUG_SOLVE")) : 0;  // timing experiments only
 
 
 #include "plan.hpp"
@@ -139,10 +102,8 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__
     const int lane = threadIdx.x & 63;
     const int o0 = blockIdx.y * OB;
     if (chunk >= ncpo) return;
-    if (BLUEST_ABLATE == 6) return;
     // where the fold expects this chunk's partials: output-major chunk numbering, or the regular rows' slots (one structure for all outputs)
     const int64_t slot = pslot ? (int64_t)pslot[chunk] : chunk, ostride = pslot ? (int64_t)slots_per_output : ncpo;
-    SPAN_BEGIN(0);
     const int64_t CH = (int64_t)iters * 256;
     const int64_t base = chunk * CH + lane * 4;
     for (int c = 0; c < n_cand; c++) {
@@ -151,7 +112,7 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__
 #pragma unroll
         for (int oo = 0; oo < OB; oo++) s[oo] = 0.0;
         double amax = 0.0;
-        for (int it = 0; it < (BLUEST_ABLATE == 9 ? 0 : iters); it++) {
+        for (int it = 0; it < iters; it++) {
             const int4 cc = load_cols4<COLT>(cols + base + it * 256);
             double2 v01[OB], v23[OB];
 #pragma unroll
@@ -161,11 +122,7 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__
                 v01[oo] = *reinterpret_cast<const double2 *>(vp);
                 v23[oo] = *reinterpret_cast<const double2 *>(vp + 2);
             }
-#if BLUEST_ABLATE == 12      // (experiment: no gather of m)
-            const double m0 = 1.0 + cc.x, m1 = 1.0 + cc.y, m2 = 1.0 + cc.z, m3 = 1.0 + cc.w;
-#else
             const double m0 = mc[cc.x], m1 = mc[cc.y], m2 = mc[cc.z], m3 = mc[cc.w];
-#endif
             amax = fmax(fmax(amax, fmax(fabs(m0), fabs(m1))), fmax(fabs(m2), fabs(m3)));
 #pragma unroll
             for (int oo = 0; oo < OB; oo++) {
@@ -179,141 +136,14 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__
 #pragma unroll
         for (int oo = 0; oo < OB; oo++) {
             const double t = wave_sum(s[oo]);
-            // (experiment builds: ABLATE 8 stores into the slots of candidate 1 -- needs max_candidates >= 2 --, so the fused kernel
-            //  reads partials that were not just rewritten; ABLATE 9 skips the streams above and only stores)
-            if (lane == 0 && o0 + oo < n_out) partial[(int64_t)(c + (BLUEST_ABLATE == 8 ? 1 : 0)) * pstride + (int64_t)(o0 + oo) * ostride + slot] = make_double2(t, amax);
+            if (lane == 0 && o0 + oo < n_out) partial[(int64_t)c * pstride + (int64_t)(o0 + oo) * ostride + slot] = make_double2(t, amax);
         }
-    }
-    SPAN_END(0, false);
-}
-
-// Phi pass FROM THE TILES (plans whose outputs share one group list, at most 32 workgroups per output): the workgroup that owns
-// tiles [b*tpb, (b+1)*tpb) of output o in the fused solve + gradient kernel also forms their contribution to Phi_o, so the plan
-// holds ONE copy of the inverses (the destination-major copy of k_phi_chunks is not built) and both passes of a step read the
-// same bytes through the same compute unit's L2: 21 MB instead of 42 at the headline size, and that does fit the 32 MB of L2.
-// No float atomics: lane = group multiplies its packed entries by m_g and leaves the products in LDS ([tile slot][entry][lane]).
-// After a barrier the products are summed per symmetric destination in an order fixed with the plan: the destination's
-// contributions (positions into the staging area) are cut into SEGMENTS of 16, one thread sums one segment (its 16 positions
-// sit in registers since the start of the kernel: 32 bytes per thread, padded with the position of a zero), a second barrier, then
-// one thread per destination adds the destination's segment sums in order and writes ONE partial per (destination, workgroup)
-// where fold_rows expects the "chunks" of the destination's row.  max |m| over the groups containing a model rides along on
-// the diagonal destinations.
-struct PhiTilesArgs {
-    const TileDesc *tiles; const RowDesc *rows; const double *tvals; const int64_t *goff; const int32_t *gmap;
-    const uint32_t *wg_seg_base;   // [bpo + 1] first segment of every workgroup
-    const uint16_t *seg_list;      // [segments][16] staging positions
-    const uint16_t *seg_dest;      // [segments] destination (bit 15: diagonal)
-    const uint16_t *wg_dseg;       // [bpo][nsym + 1] first segment (relative to the workgroup) of every destination
-    int bpo, tpb, nsym, stage_stride, seg_cap;   // seg_cap: LDS slots for segment sums (>= segments of any workgroup)
-    uint32_t stride_inv;           // ceil(2^32 / stage_stride): tile slot of a position = mulhi(pos, stride_inv)
-};
-template <int KU, int NW>
-__global__ __launch_bounds__(64 * NW) void k_phi_tiles(const PhiTilesArgs A, const double *__restrict__ m, int64_t m_stride, int n_cand,
-                                                       int64_t n_chunks, double2 *__restrict__ partial, const int32_t *__restrict__ gate)
-{
-    extern __shared__ double phi_stage[];      // [tpb * stride products][64 zeros][(tpb + 1) * 64 |m_g|, last row zero][seg_cap sums][seg_cap maxima]
-    if (gate && *gate == 0) return;   // device-side predication (SPG line-search slots)
-    if (BLUEST_ABLATE == 6) return;
-    constexpr int PU = tile_pairs(KU);
-    constexpr int NTHREADS = 64 * NW;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int tpb = A.tpb, nsym = A.nsym, S = A.stage_stride;
-    const int o = blockIdx.x / A.bpo, b = blockIdx.x % A.bpo;
-    double *stage_m = phi_stage + (int64_t)tpb * S + 64;
-    double *seg_sum = stage_m + (tpb + 1) * 64, *seg_max = seg_sum + A.seg_cap;
-    const bool has = wave < tpb;
-    TileDesc td;
-    td.k = 0; td.n_valid = 0; td.val_off = td.grad_off = 0; td.out = (int16_t)o;
-    if (has) td = A.tiles[(int64_t)blockIdx.x * tpb + wave];
-    // this thread's segment of the first pass: destination and 16 positions (two 16-byte loads)
-    const uint32_t seg0 = A.wg_seg_base[b], nseg = A.wg_seg_base[b + 1] - seg0;
-    uint4 L0 = make_uint4(0, 0, 0, 0), L1 = L0;
-    int sd0 = 0;
-    if ((uint32_t)tid < nseg) {
-        const uint4 *lp = reinterpret_cast<const uint4 *>(A.seg_list + (int64_t)(seg0 + tid) * 16);
-        L0 = lp[0]; L1 = lp[1];
-        sd0 = A.seg_dest[seg0 + tid];
-    }
-    const int k = td.k;
-    double2 pr[PU];
-    if (BLUEST_ABLATE == 11) { for (int i = 0; i < PU; i++) pr[i] = make_double2(1.0, 1.0); }      // (experiment: no tile loads)
-    else if (has && k == KU) {      // the usual tile: straight-line loads
-        const double *tl = A.tvals + td.val_off + 2 * lane;
-#pragma unroll
-        for (int i = 0; i < PU; i++) pr[i] = *reinterpret_cast<const double2 *>(tl + i * 128);
-    } else if (has && k < KU) tile_load(pr, A.tvals + td.val_off + 2 * lane, tile_pairs(k));
-    const bool valid = has && lane < (td.n_valid & 0xffff);
-    int64_t gidx = 0;
-    if (valid) {
-        const int64_t li = td.grad_off - A.goff[o] + lane;
-        gidx = A.gmap ? (int64_t)A.gmap[li] : li;
-    }
-    if (tid < 64) { phi_stage[(int64_t)tpb * S + tid] = 0.0; stage_m[tpb * 64 + tid] = 0.0; }
-    double *my_stage = phi_stage + (int64_t)wave * S + lane;
-    // sum of one segment: positions p[0..16) in order
-    auto seg_reduce = [&](const uint4 &l0, const uint4 &l1, int sd, int slot) {
-        const unsigned w[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
-        double s = 0.0;
-#pragma unroll
-        for (int h = 0; h < 2; h++) {      // eight reads in flight at a time (registers)
-            double v[8];
-#pragma unroll
-            for (int i = 0; i < 4; i++) { v[2 * i] = phi_stage[w[4 * h + i] & 0xffffu]; v[2 * i + 1] = phi_stage[w[4 * h + i] >> 16]; }
-#pragma unroll
-            for (int i = 0; i < 8; i++) s += v[i];
-        }
-        seg_sum[slot] = s;
-        if (sd & 0x8000) {     // diagonal destination: max |m| of the contributing groups
-            double am = 0.0;
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const unsigned p0 = w[i] & 0xffffu, p1 = w[i] >> 16;
-                am = fmax(am, stage_m[__umulhi(p0, A.stride_inv) * 64 + (p0 & 63)]);
-                am = fmax(am, stage_m[__umulhi(p1, A.stride_inv) * 64 + (p1 & 63)]);
-            }
-            seg_max[slot] = am;
-        }
-    };
-    for (int c = 0; c < n_cand; c++) {
-        const double mg = valid ? m[(int64_t)c * m_stride + gidx] : 0.0;
-        if (has) {
-            stage_m[wave * 64 + lane] = fabs(mg);
-#define PT(KK) case KK: if (KK <= KU) {                                                                              \
-                _Pragma("unroll") for (int e = 0; e < tile_ne(KK); e++)                                              \
-                    my_stage[e * 64] = mg * tile_slot(pr, tile_ni(KK <= KU ? KK : 1) + e);                           \
-                break; }
-            switch (k) {
-                PT(1) PT(2) PT(3) PT(4) PT(5) PT(6) PT(7) PT(8) PT(9) PT(10) PT(11) PT(12)
-                default: {      // larger groups: slots straight from global memory
-                    const double *tile = A.tvals + td.val_off;
-                    const int ni = tile_ni(k), ne = tile_ne(k);
-                    for (int e = 0; e < ne; e++) my_stage[e * 64] = mg * tile[tile_slot_off(ni + e, lane)];
-                }
-            }
-#undef PT
-        }
-        __syncthreads();
-        if (BLUEST_ABLATE == 10) continue;      // (experiment: products only)
-        if ((uint32_t)tid < nseg) seg_reduce(L0, L1, sd0, tid);
-        for (uint32_t t = tid + NTHREADS; t < nseg; t += NTHREADS) {      // (more segments than threads: rare)
-            const uint4 *lp = reinterpret_cast<const uint4 *>(A.seg_list + (int64_t)(seg0 + t) * 16);
-            seg_reduce(lp[0], lp[1], A.seg_dest[seg0 + t], (int)t);
-        }
-        __syncthreads();
-        for (int d = tid; d < nsym; d += NTHREADS) {
-            const int sb = A.wg_dseg[(int64_t)b * (nsym + 1) + d], se = A.wg_dseg[(int64_t)b * (nsym + 1) + d + 1];
-            const RowDesc rd = A.rows[(int64_t)o * nsym + d];
-            double s = 0.0, am = 0.0;
-            for (int t = sb; t < se; t++) s += seg_sum[t];
-            if (rd.a == rd.b) for (int t = sb; t < se; t++) am = fmax(am, seg_max[t]);
-            partial[(int64_t)c * n_chunks + rd.first_chunk + b] = make_double2(s, am);
-        }
-        if (c + 1 < n_cand) __syncthreads();
     }
 }
 
 // fused: fold chunk partials + solve.  grid = (n_out, n_cand), block = fold_threads (fold) -> wavefront 0 (solve).
-// want_v: bit0 = also produce v (gradient wanted); bit1 / bit2 = timing diagnostics (fold only / solve twice).
+// want_v: bit0 = also produce v (gradient wanted); bit1 / bit2 = diagnostics (fold only / solve twice)
+// that the library does not set.
 template <int NT>
 __global__ __launch_bounds__(fold_threads(NT)) void k_solve_from_chunks(int N, int n_out, const RowDesc *__restrict__ rows, int nsym, FoldReg reg,
                                                            const double2 *__restrict__ partial, int64_t n_chunks,
@@ -562,10 +392,6 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
         if (spg_state && blockIdx.x == 0 && wave == 0) spg_decide_wave(spg_state, var, status, n_out, last_slot, spg_enable, spg_ls, lane);
         return;
     }
-    if (BLUEST_ABLATE == 5) return;
-    SPAN_BEGIN(1);
-    PHASE(0);
-    PHASE_TILE(0);
     const int64_t t0 = (int64_t)blockIdx.x * tpb;      // tpb <= FUSED_TPB tiles per workgroup (wavefronts beyond it only fold)
     // which output, and am I its first workgroup: arithmetic when every output has the same number of workgroups (bpo > 0,
     // the usual case), else from the first tile's descriptor (one more dependent load in front of the fold)
@@ -575,15 +401,11 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
     SpgPrefetch pf;
     if (spg_state && first && wave == 0) spg_prefetch_state(spg_state, lane, pf);   // in flight during the fold (spg_state.hpp)
     if (N < NT) { clear_pads(lds, N, tid, NTHREADS); __syncthreads(); }   // uniform; every real entry is written by the fold
-    PHASE(1);
     // Phi either folded from this GPU's chunk partials, or (group-sharded plans) taken from the all-reduced record of output o:
     // N*N sums, then the per-model flags "touched with |m| > 1e-6" / "touched at all" and the flag "max|m| >= 0.05" as counts
     const double *rec_o = rec ? rec + (int64_t)o * (N * N + 2 * N + 1) : nullptr;
     if (rec_o) {
         for (int t = tid; t < N * N; t += NTHREADS) lds.at(t / N, t % N) = rec_o[t];
-    } else if (BLUEST_ABLATE == 1) {
-        for (int t = tid; t < N * N; t += NTHREADS) lds.at(t / N, t % N) = (t / N == t % N) ? 1.0 : 0.0;
-        if (tid < N) lds.amax[tid] = 1.0;
     } else {
         fold_rows<NT>(lds, N, rows, o * nsym, nsym, partial, tid, NTHREADS, reg);
     }
@@ -593,7 +415,6 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
     td.k = 1; td.n_valid = 0; td.val_off = td.grad_off = 0; td.out = (int16_t)o;
     if (wave > 0 && wave <= tpb) td = tiles[t0 + wave - 1];
     __syncthreads();
-    PHASE(2);
     const int k = td.k;
     double2 pr[PU];
     double V_pub = 0.0;      // wavefront 0: V and status of this workgroup's solve (for the single-output decision)
@@ -613,29 +434,19 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
         }
         double V = 0.0;
         int32_t st = 0;
-        PHASE(8);
-        if (BLUEST_ABLATE == 2) { if (lane < N) lds.vout[lane] = 1.0; }
-        else solve_wave<NT>(lds, N, delta, s1, s2, big, true, &V, lds.vout, &st, lane);
+        solve_wave<NT>(lds, N, delta, s1, s2, big, true, &V, lds.vout, &st, lane);
         if (lane == 0) { lds.status = st; if (ma.x) lds.scratch[0] = V; }      // (the elimination is done with its scratch)
         V_pub = V; st_pub = st;
         if (first) {   // first workgroup of this output publishes V, status, v
             if (lane == 0) { var[o] = V; status[o] = st; }
             if (lane < N) v_ws[(int64_t)o * N + lane] = lds.vout[lane];
         }
-        PHASE(3);
-    } else if (k <= KU && BLUEST_ABLATE != 3) {
+    } else if (k <= KU) {
         // stream the tile into registers while wavefront 0 factorises (after the fold, so these loads do not queue in front of it)
-        PHASE_TILE(1);
         if (tile_nt) tile_load<PU, true>(pr, tvals + td.val_off + 2 * lane, tile_pairs(k));
         else tile_load(pr, tvals + td.val_off + 2 * lane, tile_pairs(k));
-        PHASE_TILE(2);
-#ifdef BLUEST_PHASE_TIMING
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        PHASE_TILE(3);
-#endif
     }
     __syncthreads();
-    PHASE_TILE(4);
     if (wave == 0) {
         if (spg_state && first) {
             // SPG line search: the first workgroup of every output has published V and status above; they take a ticket and the
@@ -644,7 +455,6 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
             int last = 0;
             if (n_out == 1) {   // single output: nobody to wait for, V and status stay in lane 0's registers
                 spg_decide_wave(spg_state, var, status, n_out, last_slot, spg_enable, spg_ls, lane, pf, true, V_pub, st_pub);
-                SPAN_END(1, true);
                 return;
             }
             if (lane == 0) {
@@ -661,19 +471,13 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
                 spg_decide_wave(spg_state, var, status, n_out, last_slot, spg_enable, spg_ls, lane, pf);
             }
         }
-        SPAN_END(1, true);
         return;
     }
-    if (BLUEST_ABLATE == 3) return;
-    const bool valid = lane < (td.n_valid & 0xffff) && (BLUEST_ABLATE != 7 || pr[0].x == 1.2345);
+    const bool valid = lane < (td.n_valid & 0xffff);
     const bool inf = lds.status == BLUEST_EVAL_INF;
     double *gout = grad + td.grad_off + lane;
     // (single output, phase 1 of the second-order finish: the update itself instead of the gradient -- k_ma_update's arithmetic)
-#ifdef BLUEST_NO_MA_TAIL      // A/B build: the kernel without the tail
-    const bool MA_ON = false;
-#else
     const bool MA_ON = ma.x != nullptr;
-#endif
 #define GT(KK) case KK: if (KK <= KU) { const double q = tile_form<(KK <= KU ? KK : 1)>(pr, lds.vout);                                          \
         if (valid && !MA_ON) *gout = inf ? INFINITY : -q;                                                                                        \
         else if (valid && lds.status == BLUEST_EVAL_OK) { const int64_t i = td.grad_off + lane; const double so = ma.s[0], cci = ma.cc[i];       \
@@ -688,13 +492,6 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
         }
     }
 #undef GT
-    PHASE(4);
-    PHASE_TILE(5);
-#ifdef BLUEST_PHASE_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    PHASE_TILE(6);
-#endif
-    SPAN_END(1, false);
 }
 
 // out[c][j] = scale[j] * sum_o coef[c][o] * grad_o[c][invmap_o[j]]
@@ -1198,20 +995,7 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
         }
         const int64_t wg_per_output = std::max<int64_t>(1, ncu / n_out);
         const int64_t tpb_cu = std::max<int64_t>(1, (tiles_max + wg_per_output - 1) / wg_per_output);
-        // Phi pass from the tiles (k_phi_tiles): one group list for all outputs, at most 32 workgroups per output (the fold reads
-        // one partial per destination and workgroup), the products of a workgroup's tiles staged in LDS
-        const int64_t tpb_32 = (tiles_max + 31) / 32;
-        plan->stage_stride = tile_ne(kmax_all) * 64;
-        // LDS of k_phi_tiles (phi_tiles_lds): products + |m| row per tile slot, sums and maxima of <= stride/16 + nsym/tpb segments each
-        const int64_t tpb_lds = ((150 << 10) - 16 * (int64_t)nsym - 2048) / ((int64_t)plan->stage_stride * 9 + 512);
-        const char *tiles_env = getenv("BLUEST_PHI_TILES");        // opt-in, read per plan (profiles/r03_phi_tiles_negative_result.txt)
-        const bool want_tiles = tiles_env && atoi(tiles_env) != 0;
-        plan->phi_tiles = want_tiles && (plan->shared || n_out == 1) && tpb_32 <= std::min<int64_t>(tpb_max, tpb_lds) && kmax_all <= 16;
-        if (plan->phi_tiles) plan->fused_tpb = (int)std::min<int64_t>(std::min<int64_t>(tpb_max, tpb_lds), std::max(tpb_cu, tpb_32));
-        else plan->fused_tpb = (int)std::min<int64_t>(tpb_max, tpb_cu);
-        if (const char *tpb_env = getenv("BLUEST_TPB")) {                       // A/B switch (not for the single-copy pass)
-            if (!plan->phi_tiles && atoi(tpb_env) >= 1) plan->fused_tpb = (int)std::min<int64_t>(tpb_max, atoi(tpb_env));
-        }
+        plan->fused_tpb = (int)std::min<int64_t>(tpb_max, tpb_cu);
     }
     std::vector<TileDesc> tiles;
     std::vector<std::vector<int64_t>> bucket_val(n_out);    // first tile of size bucket k: offset
@@ -1257,7 +1041,7 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
 
     plan->identity = plan->shared && plan->outs[0].L_o == plan->L;
     for (int64_t li = 0; plan->identity && li < plan->L; li++) plan->identity = plan->outs[0].mapping[li] == li;
-    // ---- Phi pass, layout 1 (plans that cannot use k_phi_tiles): destination-major symmetric CSR, positions only ---------
+    // ---- Phi pass: destination-major symmetric CSR, positions only ---------------------------------------------------
     int iters = 1;
     int64_t CH = 256, n_chunks = 0;
     std::vector<RowDesc> rows((size_t)n_out * nsym);
@@ -1265,13 +1049,11 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
     std::vector<int64_t> out_chunk_begin(n_out + 1, 0);
     std::vector<int64_t> struct_entries(n_struct + 1, 0), struct_slots(n_struct + 1, 0);
     RawArray<int32_t> perm, cols;
-    std::vector<uint32_t> wg_seg_base;
-    std::vector<uint16_t> seg_list, seg_dest, wg_dseg;
-    std::vector<int32_t> gmap, pslot;
+    std::vector<int32_t> pslot;
     plan->fold_reg = FoldReg{0, 0, nullptr};
     std::vector<uint16_t> rank_ab;
     plan->slots_per_output = 0;
-    if (!plan->phi_tiles) {
+    {
         // parallel counting sort: slice s of S owns a contiguous range of the output's groups; it counts its entries per row,
         // the per-slice counts are prefix-summed into start offsets, then every slice writes the SLOT of its own entries -- rows
         // keep their entries in group order whatever S is, so the layout (and every summation order on the GPU) is independent
@@ -1396,74 +1178,6 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
             }
         }
         timer.lap("CSR slots + columns");
-    } else {
-        // ---- Phi pass, layout 2: per workgroup of the tile assignment and per destination, the staging positions of its products
-        const int bpo = plan->fused_bpo, tpb = plan->fused_tpb, S = plan->stage_stride;
-        iters = 0; CH = 0;
-        n_chunks = (int64_t)n_out * nsym * bpo;
-        for (int o = 0; o < n_out; o++) {
-            out_row_begin[o] = o * nsym;
-            out_chunk_begin[o] = (int64_t)o * nsym * bpo;
-            for (int a = 0; a < N; a++)
-                for (int b = a; b < N; b++) {
-                    RowDesc &rd = rows[(size_t)o * nsym + tri(a, b)];
-                    rd.first_chunk = (int32_t)(((int64_t)o * nsym + tri(a, b)) * bpo);
-                    rd.n_chunks = (int32_t)bpo;
-                    rd.out = (int16_t)o; rd.a = (int16_t)a; rd.b = (int16_t)b; rd.pad = 0;
-                }
-        }
-        out_row_begin[n_out] = n_out * nsym;
-        out_chunk_begin[n_out] = n_chunks;
-        const OutputDesc &od = plan->outs[0];
-        std::vector<int64_t> go_k(od.K + 2, 0), l0_k(od.K + 2, 0);       // first group (member offset, local index) of every size
-        for (int k = 1; k <= od.K; k++) { go_k[k + 1] = go_k[k] + od.sizes[k - 1] * k; l0_k[k + 1] = l0_k[k] + od.sizes[k - 1]; }
-        // per workgroup: contributions sorted by destination (counting sort, increasing staging position inside a destination),
-        // then cut into segments of 16 padded with the position of the zero word behind the products
-        const uint16_t zero_pos = (uint16_t)(tpb * S);
-        std::vector<std::vector<uint16_t>> lists(bpo), dests(bpo);
-        wg_dseg.assign((size_t)bpo * (nsym + 1), 0);
-        parallel_items(bpo, [&](int b) {
-            std::vector<uint32_t> cnt(nsym + 1, 0);
-            auto for_entries = [&](auto &&body) {
-                for (int j = 0; j < tpb; j++) {
-                    const TileDesc &td = tiles[(size_t)b * tpb + j];          // output 0's tiles come first in the list
-                    const int k = td.k, nv = td.n_valid & 0xffff;
-                    const int64_t li0 = td.grad_off - plan->grad_off[0];
-                    for (int e = 0, jj = 0; jj < k; jj++)
-                        for (int ll = jj; ll < k; ll++, e++)
-                            for (int lane = 0; lane < nv; lane++) {
-                                const int64_t *g = od.groups.data() + go_k[k] + (li0 + lane - l0_k[k]) * k;
-                                body(tri((int)std::min(g[jj], g[ll]), (int)std::max(g[jj], g[ll])), (uint16_t)(j * S + e * 64 + lane));
-                            }
-                }
-            };
-            for_entries([&](int d, uint16_t) { cnt[d + 1]++; });
-            for (int d = 0; d < nsym; d++) cnt[d + 1] += cnt[d];
-            std::vector<uint16_t> sorted(cnt[nsym]);
-            std::vector<uint32_t> next(cnt.begin(), cnt.end() - 1);
-            for_entries([&](int d, uint16_t pos) { sorted[next[d]++] = pos; });
-            std::vector<bool> diag(nsym, false);
-            for (int a = 0; a < N; a++) diag[tri(a, a)] = true;
-            for (int d = 0; d < nsym; d++) {
-                wg_dseg[(size_t)b * (nsym + 1) + d] = (uint16_t)dests[b].size();
-                for (uint32_t i = cnt[d]; i < cnt[d + 1]; i += 16) {
-                    for (uint32_t t = i; t < i + 16; t++) lists[b].push_back(t < cnt[d + 1] ? sorted[t] : zero_pos);
-                    dests[b].push_back((uint16_t)(d | (diag[d] ? 0x8000 : 0)));
-                }
-            }
-            wg_dseg[(size_t)b * (nsym + 1) + nsym] = (uint16_t)dests[b].size();
-        });
-        wg_seg_base.assign(bpo + 1, 0);
-        plan->seg_cap = 1;
-        for (int b = 0; b < bpo; b++) {
-            wg_seg_base[b + 1] = wg_seg_base[b] + (uint32_t)dests[b].size();
-            plan->seg_cap = std::max<int>(plan->seg_cap, (int)dests[b].size());
-            seg_list.insert(seg_list.end(), lists[b].begin(), lists[b].end());
-            seg_dest.insert(seg_dest.end(), dests[b].begin(), dests[b].end());
-        }
-        if (plan->seg_cap > 0xffff) return fail(BLUEST_ERR_ARG, "too many contribution segments per workgroup (%d)", plan->seg_cap);
-        if (!plan->identity) { gmap.resize(od.L_o); for (int64_t li = 0; li < od.L_o; li++) gmap[li] = (int32_t)od.mapping[li]; }
-        timer.lap("contribution lists");
     }
     // ---- inverse maps for combine_grad ------------------------------------------------------------
     std::vector<int32_t> invmap((size_t)n_out * plan->L, -1);
@@ -1477,9 +1191,7 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
     plan->n_rows = (int64_t)rows.size();
     plan->n_tiles = (int64_t)tiles.size();
     plan->max_cand = max_candidates;
-    plan->phi_bytes = plan->phi_tiles ? (int64_t)n_tvals * 8 + (int64_t)seg_list.size() * 2 + (int64_t)seg_dest.size() * 2 + plan->outs[0].L_o * 8 + n_chunks * 16
-                                      : n_chunks * CH * 8 + (plan->shared ? n_chunks / n_out : n_chunks) * CH * (plan->cols16 ? 2 : 4) + n_chunks * 16;
-    plan->n_segments = (int64_t)seg_dest.size();
+    plan->phi_bytes = n_chunks * CH * 8 + (plan->shared ? n_chunks / n_out : n_chunks) * CH * (plan->cols16 ? 2 : 4) + n_chunks * 16;
     plan->grad_bytes = (int64_t)n_tvals * 8 + grad_len * 8;
     {
         const char *nt_env = getenv("BLUEST_TILE_NT");              // A/B switch, read per plan: 0 = plain loads
@@ -1497,9 +1209,6 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
     const size_t o_goff = arena.reserve(plan->grad_off.size() * sizeof(int64_t));
     const size_t o_perm = arena.reserve(perm.size() * sizeof(int32_t));
     const size_t o_ocb = arena.reserve(out_chunk_begin.size() * sizeof(int64_t));
-    const size_t o_segbase = arena.reserve(wg_seg_base.size() * sizeof(uint32_t)), o_seglist = arena.reserve(seg_list.size() * sizeof(uint16_t));
-    const size_t o_segdest = arena.reserve(seg_dest.size() * sizeof(uint16_t)), o_dseg = arena.reserve(wg_dseg.size() * sizeof(uint16_t));
-    const size_t o_gmap = arena.reserve(gmap.size() * sizeof(int32_t));
     const size_t o_partial = arena.reserve((size_t)max_candidates * plan->partial_stride * sizeof(double2));
     const size_t o_pslot = arena.reserve(pslot.size() * sizeof(int32_t)), o_rankab = arena.reserve(rank_ab.size() * sizeof(uint16_t));
     const size_t o_v = arena.reserve((size_t)max_candidates * n_out * N * sizeof(double));
@@ -1512,7 +1221,7 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
     plan->d_tvals = reinterpret_cast<double *>(arena.base + o_tvals);
     int32_t *d_perm = nullptr;
     // clear what the scatter kernels do not write (padding slots, padding lanes); then the small tables
-    if (!plan->phi_tiles) HIP_TRY(hipMemsetAsync(plan->d_vals, 0, (size_t)n_chunks * CH * sizeof(double), 0));
+    HIP_TRY(hipMemsetAsync(plan->d_vals, 0, (size_t)n_chunks * CH * sizeof(double), 0));
     HIP_TRY(hipMemsetAsync(plan->d_tvals, 0, n_tvals * sizeof(double), 0));
     // columns: the structure's list sits at the structure's own chunk range (shared plans: output 0's range is the one the
     // Phi kernel reads; the other ranges stay unused)
@@ -1520,11 +1229,11 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
         RawArray<uint16_t> c16(cols.size());
         for (size_t i = 0; i < cols.size(); i++) c16.data()[i] = (uint16_t)cols.data()[i];
         uint16_t *d16 = reinterpret_cast<uint16_t *>(plan->d_cols);
-        for (int o = 0; o < n_struct && !plan->phi_tiles; o++)
+        for (int o = 0; o < n_struct; o++)
             HIP_TRY(hipMemcpy(d16 + out_chunk_begin[o] * CH, c16.data() + struct_slots[o],
                               (size_t)(struct_slots[o + 1] - struct_slots[o]) * sizeof(uint16_t), hipMemcpyHostToDevice));
     } else
-    for (int o = 0; o < n_struct && !plan->phi_tiles; o++)
+    for (int o = 0; o < n_struct; o++)
         HIP_TRY(hipMemcpy(plan->d_cols + out_chunk_begin[o] * CH, cols.data() + struct_slots[o],
                           (size_t)(struct_slots[o + 1] - struct_slots[o]) * sizeof(int32_t), hipMemcpyHostToDevice));
     if ((rc = upload(arena, o_rows, &plan->d_rows, rows))) return rc;
@@ -1534,11 +1243,6 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
     if ((rc = upload(arena, o_goff, &plan->d_goff, plan->grad_off))) return rc;
     if ((rc = upload(arena, o_perm, &d_perm, perm))) return rc;
     if ((rc = upload(arena, o_ocb, &plan->d_out_chunk_begin, out_chunk_begin))) return rc;
-    if ((rc = upload(arena, o_segbase, &plan->d_wg_seg_base, wg_seg_base))) return rc;
-    if ((rc = upload(arena, o_seglist, &plan->d_seg_list, seg_list))) return rc;
-    if ((rc = upload(arena, o_segdest, &plan->d_seg_dest, seg_dest))) return rc;
-    if ((rc = upload(arena, o_dseg, &plan->d_wg_dseg, wg_dseg))) return rc;
-    if ((rc = upload(arena, o_gmap, &plan->d_gmap, gmap))) return rc;
     if ((rc = upload(arena, o_pslot, &plan->d_pslot, pslot))) return rc;
     if (pslot.empty()) plan->d_pslot = nullptr;
     {
@@ -1546,7 +1250,6 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
         if ((rc = upload(arena, o_rankab, &d_rank_ab, rank_ab))) return rc;
         plan->fold_reg.rank_ab = rank_ab.empty() ? nullptr : d_rank_ab;
     }
-    if (gmap.empty()) plan->d_gmap = nullptr;
     plan->max_chunks_per_output = 0;
     for (int o = 0; o < n_out; o++) plan->max_chunks_per_output = std::max<int>(plan->max_chunks_per_output, (int)(out_chunk_begin[o + 1] - out_chunk_begin[o]));
     timer.lap("device arena + small uploads");
@@ -1559,7 +1262,6 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
             const int64_t Lk = od.sizes[k - 1];
             const int ne = k * (k + 1) / 2;
             if (Lk > 0) {
-                if (!plan->phi_tiles)
                 hipLaunchKernelGGL(k_fill_csr, dim3((unsigned)((Lk * ne + 255) / 256)), dim3(256), 0, 0, od.d_invcov + io, k, Lk,
                                    d_perm + struct_entries[st] + eo, plan->d_vals + out_chunk_begin[o] * CH);
                 hipLaunchKernelGGL(k_fill_tiles, dim3((unsigned)((Lk * (ne + k) + 255) / 256)), dim3(256), 0, 0, od.d_invcov + io,
@@ -1736,63 +1438,28 @@ static void launch_grad(bluest_plan_t plan, const double *v_dev, const int32_t *
 #undef LG
 }
 
-// dynamic LDS of k_phi_tiles: products, 64 zeros, |m| rows (one more, zero), segment sums and maxima
-static size_t phi_tiles_lds(int tpb, int stage_stride, int seg_cap)
-{
-    return ((size_t)tpb * stage_stride + 64 + (size_t)(tpb + 1) * 64 + 2 * (size_t)seg_cap) * sizeof(double);
-}
-
 static void launch_chunks(bluest_plan_t p, const double *m, int n_cand, int64_t m_stride, hipStream_t st)
 {
     const int n_out = (int)p->outs.size();
-    if (p->phi_tiles) {
-        int kmax = 0;
-        for (const auto &od : p->outs) kmax = std::max(kmax, od.K);
-        const size_t lds = phi_tiles_lds(p->fused_tpb, p->stage_stride, p->seg_cap);
-        const dim3 grid((unsigned)(p->n_tiles / p->fused_tpb));
-        PhiTilesArgs A;
-        A.tiles = p->d_tiles; A.rows = p->d_rows; A.tvals = p->d_tvals; A.goff = p->d_goff; A.gmap = p->d_gmap;
-        A.wg_seg_base = p->d_wg_seg_base; A.seg_list = p->d_seg_list; A.seg_dest = p->d_seg_dest; A.wg_dseg = p->d_wg_dseg;
-        A.bpo = p->fused_bpo; A.tpb = p->fused_tpb; A.nsym = p->nsym; A.stage_stride = p->stage_stride; A.seg_cap = p->seg_cap;
-        A.stride_inv = (uint32_t)((0x100000000ull + (uint64_t)p->stage_stride - 1) / (uint64_t)p->stage_stride);
-        // same block size as the fused kernel of this plan (16 wavefronts while the tile fits 128 registers, else 8)
-#define LPT(KU, NW) do {                                                                                                          \
-            static size_t lds_set = 0;     /* dynamic LDS beyond 64 KB has to be declared once per kernel */                     \
-            if (lds > lds_set) { (void)hipFuncSetAttribute((const void *)k_phi_tiles<KU, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set = lds; } \
-            hipLaunchKernelGGL((k_phi_tiles<KU, NW>), grid, dim3(64 * NW), lds, st, A, m, m_stride, n_cand, p->partial_stride, p->d_partial, p->gate); \
-        } while (0)
-        const bool wide = fused_tpb(pick_nt(p->N), pick_ku(kmax)) == 15;
-        // groups of up to 5 models keep their tile in registers; larger ones read the slots from (L2-resident) global memory in
-        // the product phase -- with the tile AND the segment positions in registers the 1024-thread form would spill
-        if (kmax <= 5) { if (wide) LPT(5, 16); else LPT(5, 8); }
-        else { if (wide) LPT(1, 16); else LPT(1, 8); }
-#undef LPT
-        return;
-    }
-    // wavefronts per workgroup of the chunk kernels: single-wavefront workgroups drain earliest at the kernel's end (same-box A/B
-    // at the headline size, two runs each: step 12.86 / 12.26 / 12.05 us with 4 / 2 / 1 wavefronts, 13.8 with 16)
-    static const int wpb = getenv("BLUEST_PHI_WPB") ? atoi(getenv("BLUEST_PHI_WPB")) : 1;
+    // one wavefront per workgroup of the chunk kernels (WPB = 1): single-wavefront workgroups drain earliest at the kernel's end
+    // (same-box A/B at the headline size, two runs each: step 12.86 / 12.26 / 12.05 us with 4 / 2 / 1 wavefronts, 13.8 with 16)
     if (p->shared && n_out >= 2) {
         const int64_t ncpo = p->n_chunks / n_out;
         // outputs per wavefront: sharing the column stream saves bytes, but the pass is latency-bound, so keep at least
         // ~4096 wavefronts in flight (measured at n=20, n_out=8: OB=8 6.9 us, OB=4 5.5 us, OB=2 5.1 us, OB=1 6.1 us)
         int ob = 8;
         while (ob > 2 && (ncpo * ((n_out + ob - 1) / ob) < 4096 || ob > n_out)) ob /= 2;
-        static const int ob_env = getenv("BLUEST_PHI_OB") ? atoi(getenv("BLUEST_PHI_OB")) : 0;        // A/B switch
-        if (ob_env == 2 || ob_env == 4 || ob_env == 8) ob = ob_env;
-#define LCS2(OB, WPB, COLT) hipLaunchKernelGGL((k_phi_chunks_shared<OB, WPB, COLT>), dim3((unsigned)((ncpo + WPB - 1) / WPB), (n_out + OB - 1) / OB), dim3(64 * WPB), 0, st, \
-                                        p->d_vals, reinterpret_cast<const COLT *>(p->d_cols), p->iters, ncpo, n_out, m, m_stride, n_cand, p->partial_stride, p->d_pslot, p->slots_per_output, p->d_partial, p->gate)
-#define LCS(OB, WPB) do { if (p->cols16) LCS2(OB, WPB, uint16_t); else LCS2(OB, WPB, int32_t); } while (0)
-        if (wpb == 1) { if (ob == 8) LCS(8, 1); else if (ob == 4) LCS(4, 1); else LCS(2, 1); }
-        else { if (ob == 8) LCS(8, 4); else if (ob == 4) LCS(4, 4); else LCS(2, 4); }
+#define LCS2(OB, COLT) hipLaunchKernelGGL((k_phi_chunks_shared<OB, 1, COLT>), dim3((unsigned)ncpo, (n_out + OB - 1) / OB), dim3(64), 0, st, \
+                                   p->d_vals, reinterpret_cast<const COLT *>(p->d_cols), p->iters, ncpo, n_out, m, m_stride, n_cand, p->partial_stride, p->d_pslot, p->slots_per_output, p->d_partial, p->gate)
+#define LCS(OB) do { if (p->cols16) LCS2(OB, uint16_t); else LCS2(OB, int32_t); } while (0)
+        if (ob == 8) LCS(8); else if (ob == 4) LCS(4); else LCS(2);
 #undef LCS
 #undef LCS2
         return;
     }
-#define LPC(WPB, COLT) hipLaunchKernelGGL((k_phi_chunks<WPB, COLT>), dim3((unsigned)((p->n_chunks + WPB - 1) / WPB)), dim3(64 * WPB), 0, st, p->d_vals, \
-                                       reinterpret_cast<const COLT *>(p->d_cols), p->iters, p->n_chunks, m, m_stride, n_cand, p->d_partial, p->d_pslot, p->partial_stride, p->gate)
-    if (wpb == 1) { if (p->cols16) LPC(1, uint16_t); else LPC(1, int32_t); }
-    else { if (p->cols16) LPC(4, uint16_t); else LPC(4, int32_t); }
+#define LPC(COLT) hipLaunchKernelGGL((k_phi_chunks<1, COLT>), dim3((unsigned)p->n_chunks), dim3(64), 0, st, p->d_vals, \
+                                  reinterpret_cast<const COLT *>(p->d_cols), p->iters, p->n_chunks, m, m_stride, n_cand, p->d_partial, p->d_pslot, p->partial_stride, p->gate)
+    if (p->cols16) LPC(uint16_t); else LPC(int32_t);
 #undef LPC
 }
 
@@ -1925,7 +1592,7 @@ static int plan_eval(bluest_plan_t plan, const double *m_dev, int n_cand, int64_
     hipStream_t st = (hipStream_t)stream;
     const int n_out = (int)plan->outs.size();
     int32_t *status = status_dev ? status_dev : plan->d_status;
-    if (plan->matfree && n_cand == 1 && !dec_state && !plan->gate && !g_debug_solve) {
+    if (plan->matfree && n_cand == 1 && !dec_state && !plan->gate) {
         // matrix-free: Phi pass -> record -> (solve + gradient | solve) -- no stored inverse is read
         const double *rec = nullptr;
         if ((rc = mf_phi_record(plan, m_dev, nullptr, &rec, st))) return rc;
@@ -1938,12 +1605,12 @@ static int plan_eval(bluest_plan_t plan, const double *m_dev, int n_cand, int64_
         return BLUEST_OK;
     }
     launch_chunks(plan, m_dev, n_cand, m_stride, st);
-    if (plan->mf_gradient && grad_dev && n_cand == 1 && !dec_state && !plan->gate && !g_debug_solve)
+    if (plan->mf_gradient && grad_dev && n_cand == 1 && !dec_state && !plan->gate)
         return mf_solve_grad(plan, nullptr, delta, var_dev, status, grad_dev, st, ma);  // stored Phi pass + fold, solve and matrix-free gradient
     int kmax = 0;
     for (const auto &od : plan->outs) kmax = std::max(kmax, od.K);
     // fused solve + gradient pass (2 launches per evaluation); groups larger than 12 take the generic tile code inside it
-    if (grad_dev && n_cand == 1 && !g_debug_solve) {
+    if (grad_dev && n_cand == 1) {
         const dim3 grid((unsigned)(plan->n_tiles / plan->fused_tpb));
 #define LSG2(NT, KU) hipLaunchKernelGGL((k_solve_grad<NT, KU>), grid, dim3(64 * (fused_tpb(NT, KU) + 1)), 0, st, plan->N, n_out, plan->d_rows, plan->nsym, plan->fold_reg, plan->d_partial, nullptr, \
                                         delta, plan->d_tiles, plan->n_tiles, plan->fused_bpo, plan->fused_tpb, plan->tile_nt ? 1 : 0, plan->d_tvals, var_dev, plan->d_v, status, grad_dev, plan->gate, \
@@ -1955,7 +1622,7 @@ static int plan_eval(bluest_plan_t plan, const double *m_dev, int n_cand, int64_
         HIP_TRY(hipGetLastError());
         return BLUEST_OK;
     }
-    const int want = ((grad_dev || plan->always_v) ? 1 : 0) | g_debug_solve;
+    const int want = (grad_dev || plan->always_v) ? 1 : 0;
 #define LSC(NT) hipLaunchKernelGGL((k_solve_from_chunks<NT>), dim3(n_out, n_cand), dim3(fold_threads(NT)), 0, st, plan->N, n_out, plan->d_rows, \
                                    plan->nsym, plan->fold_reg, plan->d_partial, plan->partial_stride, delta, want, var_dev, plan->d_v, status, plan->gate, \
                                    dec_state, dec_last, dec_enable, plan->d_ticket)
@@ -1984,7 +1651,7 @@ extern "C" int bluest_plan_eval_ma(bluest_plan_t plan, double *m_dev, double *va
     if (!plan->finalized) return fail(BLUEST_ERR_STATE, "plan not finalized");
     int kmax = 0;
     for (const auto &od : plan->outs) kmax = std::max(kmax, od.K);
-    if (plan->outs.size() != 1 || !plan->identity || plan->gate || g_debug_solve || kmax > (plan->matfree ? 8 : 12))
+    if (plan->outs.size() != 1 || !plan->identity || plan->gate || kmax > (plan->matfree ? 8 : 12))
         return fail(BLUEST_ERR_STATE, "bluest_plan_eval_ma: one output on all groups under the identity mapping only");
     // (the gradient pointer only selects the fused kernel: with the tail on, nothing is written through it)
     return plan_eval(plan, m_dev, 1, 0, 0.0, var_dev, plan->d_v, plan->grad_len, status_dev, stream, nullptr, 0, nullptr, MaTail{x_dev, cc_dev, m_dev, s_dev});

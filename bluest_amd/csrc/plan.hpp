@@ -63,17 +63,6 @@ struct bluest_plan_s {
     int32_t *d_out_row_begin = nullptr;
     int64_t *d_out_chunk_begin = nullptr;   // n_out + 1: first chunk of every output (its partials are contiguous)
     int max_chunks_per_output = 0;
-    // Phi pass from the tiles (k_phi_tiles): the plan keeps ONE copy of the inverses.  Per workgroup of the fused kernel's tile
-    // assignment and per symmetric destination, the list of that workgroup's contributions as positions into its LDS staging area
-    bool phi_tiles = false;
-    int stage_stride = 0;               // doubles of staging per tile slot of a workgroup: ne(k_max) * 64
-    int seg_cap = 0;                    // most segments any workgroup has
-    uint32_t *d_wg_seg_base = nullptr;  // [bpo + 1]
-    uint16_t *d_seg_list = nullptr;     // [segments][16] staging positions (tile slot * stage_stride + entry * 64 + lane)
-    uint16_t *d_seg_dest = nullptr;     // [segments] destination, bit 15 = diagonal
-    uint16_t *d_wg_dseg = nullptr;      // [bpo][nsym + 1]
-    int32_t *d_gmap = nullptr;          // local group index -> global index (NULL: identity)
-    int64_t n_segments = 0;
     TileDesc *d_tiles = nullptr;
     double *d_tvals = nullptr;   // tiles: slot pairs (see TileDesc)
     int32_t *d_invmap = nullptr;

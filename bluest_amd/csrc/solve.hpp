@@ -3,10 +3,6 @@
 #pragma once
 #include "common.hpp"
 
-#ifndef PHASE          // in-kernel timestamps exist only in the experiment build of plan.hip
-#define PHASE(i)
-#endif
-
 struct RowDesc {      // one symmetric destination (a <= b) of one output
     int32_t first_chunk;
     int32_t n_chunks;
@@ -413,7 +409,6 @@ __device__ __forceinline__ void solve_wave(SolveLds<NT> &lds, int N, double delt
             const bool mine = (NT - 1 - p) < N && ((mask >> (NT - 1 - p)) & 1ull);
             const double *row = lds.phi + (NT - 1 - mp) * LDP;
             double a[NT];
-            PHASE(9);
 #pragma unroll
             for (int c = 0; c < NT; c += 2) {
                 const double2 x = *reinterpret_cast<const double2 *>(row + c);
@@ -441,9 +436,7 @@ __device__ __forceinline__ void solve_wave(SolveLds<NT> &lds, int N, double delt
             }
             double last_pivot = 1.0;
             int bad = 0;
-            PHASE(5);
             const double x = gj_solve_last<NT>(a, lane, diag0, lds.scratch, last_pivot, bad);      // x = A^-1 e_last at position p
-            PHASE(6);
             if (__builtin_expect(uniform_i(bad) != 0, 0)) {
                 if (status == BLUEST_EVAL_OK) status = BLUEST_EVAL_SINGULAR;
                 if (pass == 0) V = NAN;
@@ -460,7 +453,6 @@ __device__ __forceinline__ void solve_wave(SolveLds<NT> &lds, int N, double delt
             }
         }
     }
-    PHASE(7);
     if (want_v) {   // position p holds model NT-1-p (0 <-> vswap exchanged)
         int mp = NT - 1 - p;
         if (vswap != 0) mp = (mp == 0) ? vswap : (mp == vswap ? 0 : mp);

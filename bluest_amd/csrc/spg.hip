@@ -1037,18 +1037,15 @@ static int simplex_impl(const double *x_dev, const double *g_dev, double lambda,
                 ncu_of[dev] = prop.multiProcessorCount;
             }
             const int ncu = ncu_of[dev];
-            static int maxp = getenv("BLUEST_PROJ_MAXP") ? atoi(getenv("BLUEST_PROJ_MAXP")) : (int)FusedProj::MAXP;   // timing experiments
-            static int bracket = getenv("BLUEST_PROJ_NO_BRACKET") ? 0 : 1;   // timing experiments
-            static int maxb = getenv("BLUEST_PROJ_MAXB") ? atoi(getenv("BLUEST_PROJ_MAXB")) : 64;   // 64 measured best at L = 245505 (61 -> 42 us)
             // workgroup size: 256 threads when 64 of them hold the vector with <= 4 entries per thread (K_tot <= 65536), else 1024
-            static int bt_env = getenv("BLUEST_PROJ_THREADS") ? atoi(getenv("BLUEST_PROJ_THREADS")) : 0;   // timing experiments
-            const int bt = bt_env ? bt_env : (L <= 64LL * 256 * 4 ? 256 : 1024);
+            const int bt = L <= 64LL * 256 * 4 ? 256 : 1024;
             const int nb_bt = (int)((L + bt - 1) / bt);
-            const int nbf = std::max(1, std::min(std::min(nb_bt, ncu), std::min(std::min(maxb, 64), (int)FusedProj::MAXB)));   // <= 64: one wavefront folds the messages
+            // at most 64 workgroups (one wavefront folds the messages; 64 measured best at L = 245505: 61 -> 42 us)
+            const int nbf = std::max(1, std::min(std::min(nb_bt, ncu), 64));
             const int64_t items = (L + (int64_t)bt * nbf - 1) / ((int64_t)bt * nbf);
             if (items <= 16 && !getenv("BLUEST_PROJ_MULTI_LAUNCH")) {
 #define PF(IT) hipLaunchKernelGGL((k_proj_fused<IT>), dim3(nbf), dim3(bt), 0, st, x_dev, g_dev, lambda, z, floor, L, ws, nb, p_dev, d_dev, \
-                                  stats_dev, spg_state, spg_mode, trial_scale, trial_xnew, trial_m, trial_enable, maxp, bracket)
+                                  stats_dev, spg_state, spg_mode, trial_scale, trial_xnew, trial_m, trial_enable, (int)FusedProj::MAXP, /* bracket */ 1)
                 if (items <= 1) PF(1); else if (items <= 2) PF(2); else if (items <= 4) PF(4); else if (items <= 8) PF(8); else PF(16);
 #undef PF
                 HIP_TRY(hipGetLastError());

@@ -15,7 +15,7 @@ import time
 import numpy as np
 import torch
 
-from ._lib import capture_guard, check
+from ._lib import check
 from .plan import EVAL_OK, _stream, projection_workspace, simplex_project
 
 # state layout (csrc/spg.hip SPG_*)
@@ -36,7 +36,6 @@ class DeviceSpg(object):
         self.scale_h = self.scale.cpu().numpy()
         # NOTE: no torch compute operator is used anywhere on this path (only allocations and copies): on ROCm the first use
         # of each torch operator loads its kernels, 30-150 ms a piece, which used to triple the first solve of a process
-        self._one = torch.from_numpy(np.ones(1)).to(self.dev)
         self._zero = torch.from_numpy(np.zeros(1)).to(self.dev)
         self.s_norm = np.asarray(s_norm, dtype=np.float64)
         self.p, self.floor = float(p), float(floor)
@@ -56,43 +55,18 @@ class DeviceSpg(object):
         v = ctypes.c_void_p()
         check(self.lib.bluest_plan_v_workspace(self.hip._h, ctypes.byref(v), None))
         self.v_ws = v.value
-        self.graph_sets = {}          # hipGraphs per number of in-iteration line-search slots
         self.window_seconds = []
-        self.graphs = None
 
-    # ---- launch sequences (captured into hipGraphs) -------------------------------------------------------------
+    # ---- launch sequences ---------------------------------------------------------------------------------------
     def _direction(self):
         """d = P_s(x - lambda s g) - x and, fused, the first trial point (alpha = 1) + open gate"""
         check(self.lib.bluest_spg_direction(self.x.data_ptr(), self.g.data_ptr(), self.st.data_ptr(), 1.0, self.floor, self.L,
                                             self.d.data_ptr(), self.scale.data_ptr(), self.xnew.data_ptr(), self.m.data_ptr(),
                                             self.enable.data_ptr(), self.pws.data_ptr(), _stream()))
 
-    def _slot(self, t, with_trial):
-        if with_trial:
-            check(self.lib.bluest_spg_trial(self.x.data_ptr(), self.d.data_ptr(), self.scale.data_ptr(), self.st.data_ptr(),
-                                            self.xnew.data_ptr(), self.m.data_ptr(), self.enable.data_ptr(), self.L, _stream()))
-        # Phi pass, then solve with the line-search decision fused into its tail (csrc/plan.hip: k_solve_from_chunks)
-        check(self.lib.bluest_plan_eval_decide(self.hip._h, self.m.data_ptr(), 0.0, self.var.data_ptr(), self.status.data_ptr(),
-                                               self.st.data_ptr(), 1 if t == self.T - 1 else 0, self.enable.data_ptr(), _stream()))
-
-    def _finish(self):
-        check(self.lib.bluest_spg_finish(self.hip._h, self.v_ws, self.status.data_ptr(), self.x.data_ptr(), self.g.data_ptr(),
-                                         self.xnew.data_ptr(), self.grad.data_ptr(), self.scale.data_ptr(), self.st.data_ptr(),
-                                         self.floor, self.work.data_ptr(), _stream()))
-
     def _converged(self):
         check(self.lib.bluest_spg_converged(self.x.data_ptr(), self.g.data_ptr(), self.st.data_ptr(), 1.0, self.floor, self.L,
                                             self.pws.data_ptr(), _stream()))
-
-    def _iteration(self):
-        self._direction()
-        for t in range(self.T):
-            self._slot(t, t > 0)
-        self._finish()
-
-    def _iteration_checked(self):
-        self._iteration()
-        self._converged()
 
     def _window_direct(self, n_iterations, check_last):
         """n whole iterations (+ the convergence projection) enqueued by ONE call into the library: plain stream launches"""
@@ -101,41 +75,6 @@ class DeviceSpg(object):
                                          self.status.data_ptr(), self.grad.data_ptr(), self.enable.data_ptr(), self.work.data_ptr(),
                                          self.pws.data_ptr(), self.v_ws, self.floor, self.T, int(n_iterations), 1 if check_last else 0,
                                          _stream()))
-
-    def _window(self):
-        """check_every iterations, the last one with the convergence projection: ONE graph replay per host look
-        (a replay per iteration costs ~8 us more per iteration in launch overhead, tools/spg_floor.py)"""
-        for _ in range(self.check_every - 1):
-            self._iteration()
-        self._iteration_checked()
-
-    def _capture(self, fn):
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):
-            saved = torch.empty_like(self.st)
-            saved.copy_(self.st)
-            self.st[DONE:DONE + 1].copy_(self._one)   # warm-up outside capture with every kernel predicated off
-            fn()
-            self.st.copy_(saved)
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        torch.cuda.synchronize(self.dev)
-        g = torch.cuda.CUDAGraph()
-        # Anything that frees device memory or destroys a hipGraph on this thread while the capture runs invalidates it
-        # (hipErrorStreamCaptureInvalidated).  Plans and solver graphs dropped meanwhile -- by the cyclic collector OR by a
-        # reference count reaching zero -- are parked by the library / by capture_guard and released after the capture.
-        with capture_guard():
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                fn()
-        return g
-
-    def __del__(self):
-        try:
-            graphs = [g for gs in self.graph_sets.values() for g in gs.values()]
-            self.graph_sets = {}
-            capture_guard.park(graphs)
-        except Exception:
-            pass
 
     def _check_replicas(self, hs):
         """hook of the collective variant: all ranks must have seen the same state (no-op on one GPU)"""
@@ -154,14 +93,9 @@ class DeviceSpg(object):
         t = (r / rmax) ** self.p
         return rmax * t.sum() ** (1.0 / self.p), (r / rmax) ** (self.p - 1) * t.sum() ** (1.0 / self.p - 1.0) / self.s_norm
 
-    def run(self, x0, eps=1e-7, maxit=2000, max_fevals=10 ** 6, use_graph=None, rel_tol=0.0, stall_window=100):
-        """use_graph: None = the default (direct launches of a whole window by one library call; BLUEST_SPG_GRAPH=1 in the
-        environment selects hipGraph replay), True = captured hipGraphs, False = direct launches"""
+    def run(self, x0, eps=1e-7, maxit=2000, max_fevals=10 ** 6, rel_tol=0.0, stall_window=100):
         plan, lib, st = self.plan, self.lib, self.st
         del self.window_seconds[:]                                  # diagnostics of THIS run only
-        if use_graph is None:
-            import os
-            use_graph = bool(os.environ.get("BLUEST_SPG_GRAPH"))
         with torch.cuda.device(self.dev):
             check(lib.bluest_plan_set_gate(self.hip._h, None, 0))
             if not isinstance(x0, torch.Tensor):
@@ -190,24 +124,6 @@ class DeviceSpg(object):
             st.copy_(torch.from_numpy(h))
             check(lib.bluest_plan_set_gate(self.hip._h, self.enable.data_ptr(), 1))
             try:
-                def bind():
-                    """launchers of one step, one step + convergence projection, and a whole window; every hipGraph is captured
-                    when it is first needed"""
-                    if not use_graph:
-                        return (lambda: self._window_direct(1, False), lambda: self._window_direct(1, True),
-                                lambda: self._window_direct(self.check_every, True))
-                    gs = self.graph_sets.setdefault(self.T, {})
-
-                    def lazy(name, fn):
-                        def replay():
-                            if name not in gs:
-                                gs[name] = self._capture(fn)
-                            gs[name].replay()
-                        return replay
-                    self.graphs = gs
-                    return lazy("iteration", self._iteration), lazy("iteration_checked", self._iteration_checked), lazy("window", self._window)
-
-                run_iter, run_iter_checked, run_window = bind()
                 info, it, count = 1, 0, 1
                 stalled = False
                 hs = h
@@ -229,12 +145,7 @@ class DeviceSpg(object):
                         break
                     nrun = min(self.check_every, maxit - it)
                     t_window = time.perf_counter()
-                    if nrun == self.check_every:
-                        run_window()                            # the whole window is one graph
-                    else:
-                        for _ in range(nrun - 1):
-                            run_iter()
-                        run_iter_checked()                      # last one also measures gpmax (sets DONE when <= eps)
+                    self._window_direct(nrun, True)             # the last iteration also measures gpmax (sets DONE when <= eps)
                     hs = st.cpu().numpy()
                     self.window_seconds.append(time.perf_counter() - t_window)      # host-visible time of the window (diagnostics)
                     self._check_replicas(hs)
@@ -330,6 +241,3 @@ class ShardedDeviceSpg(DeviceSpg):
         if not np.array_equal(t[:len(v)], -t[len(v):]):
             raise RuntimeError("sharded SPG: the replicated solver states of the ranks differ (max %s, min %s)" % (t[:len(v)], -t[len(v):]))
 
-    def run(self, x0, **kwargs):
-        kwargs["use_graph"] = False                               # collectives are enqueued directly
-        return super().run(x0, **kwargs)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of one environment switch on the SAME box: rocprofv3 kernel statistics of tools/one_solve.py with and without it.
-#   bash tools/ab_kernel_stats.sh BLUEST_PROJ_NO_BRACKET [n k n_out]
+#   bash tools/ab_kernel_stats.sh BLUEST_PROJ_MULTI_LAUNCH [n k n_out]
 VAR=$1; shift
 ARGS=${@:-20 5 8 3}
 cd /tmp && export TMPDIR=/tmp

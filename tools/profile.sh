@@ -59,8 +59,7 @@ PY
   grep rep $OUT/solve_$tagc.log >> $SUM/${TAG}_solve_kernel_stats_$tagc.txt
 done
 echo "solve stats done"
-# (6) master phases (experiment build, product build restored), parts of a step on the chain clock, quality sweep
-bash tools/master_phases.sh $SUM/${TAG}_master_phases.txt > /dev/null 2>&1
+# (6) parts of a step on the chain clock, quality sweep
 python tools/step_parts.py > $SUM/${TAG}_step_parts.txt 2>/dev/null
 python tools/matfree_ab.py 25 6 1 20 5 8 20 5 1 > $SUM/${TAG}_matfree_ab_final.txt 2>/dev/null
 python tools/batch_bench.py > $SUM/${TAG}_batch_bench.txt 2>/dev/null; python tools/batch_bench.py 25 6 1 >> $SUM/${TAG}_batch_bench.txt 2>/dev/null; python tools/batch_bench.py 20 5 1 >> $SUM/${TAG}_batch_bench.txt 2>/dev/null

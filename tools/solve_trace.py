@@ -38,19 +38,6 @@ def logged(self, x0, **kw):
 
 
 spg_device.DeviceSpg.run = logged
-orig_capture = spg_device.DeviceSpg._capture
-
-
-def timed_capture(self, fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    g = orig_capture(self, fn)
-    torch.cuda.synchronize()
-    print("    capture %-20s L=%d T=%d: %.1f ms" % (fn.__name__, self.L, self.T, 1e3 * (time.perf_counter() - t0)))
-    return g
-
-
-spg_device.DeviceSpg._capture = timed_capture
 import gc
 run_total = [0.0]
 _logged = spg_device.DeviceSpg.run
