@@ -18,8 +18,12 @@ timing   : W warm-up steps, then exactly K timed steps queued right behind them,
            (ms_per_step = elapsed / K; `repeats` is 1).
 outputs  : --dump-outputs DIR writes what the last timed step returned (V, grad V and status of every output) as DIR/<name>.npy
            in float64, so that two builds can be compared output for output on the same seeded inputs.
+legs     : a plain run sets up, warms up, times the K steps, checks their status, writes --dump-outputs and prints the line.
+           --full adds every other leg: per-kernel times and the roofline, the batched throughput, the SAP wall-clock and the
+           CPU baselines (one GPU); the check against the unsharded evaluation, the single-GPU and replica figures, the batched
+           sharded step and the sharded solve (N > 1).  --no-batched / --no-sap / --no-cpu-baseline drop legs of a --full run.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -424,9 +428,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sap", action="store_true", help="skip the SAP wall-clock leg (covariances -> continuous optimum)")
-    ap.add_argument("--no-batched", action="store_true", help="skip the batched-throughput leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's steps, also run every other leg (kernel times, roofline, batched, SAP wall-clock, "
+                         "CPU baselines; N > 1: sharded check, single-GPU and replica figures, sharded solve)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-sap", action="store_true", help="--full: skip the SAP wall-clock leg (covariances -> continuous optimum)")
+    ap.add_argument("--no-batched", action="store_true", help="--full: skip the batched-throughput leg")
     ap.add_argument("--no-graph", action="store_true", help="launch every step eagerly instead of replaying a hipGraph")
     ap.add_argument("--graph-steps", type=int, default=40, help="steps captured per hipGraph (capped at --steps)")
     ap.add_argument("--shard", choices=["auto", "candidates", "outputs", "groups"], default="auto")
@@ -481,6 +488,7 @@ def main():
     if shard == "outputs" and n_out_all % world:
         raise SystemExit("--shard outputs needs n_out divisible by the number of GPUs")
     BATCHES = (4, 16)
+    # the plans are sized for the batched legs whether or not --full runs them, so that every run times the same plan
     max_cand = max(BATCHES) if (world == 1 and not args.no_batched) else 1
     my_outputs = list(range(n_out_all))
     sharded = None
@@ -544,7 +552,7 @@ def main():
                      "" if world == 1 else "_rank%d" % rank)
 
     extra = {}
-    if world > 1 and not weak:
+    if world > 1 and not weak and args.full:
         # outside the timed region: (1) the sharded evaluation equals the unsharded one; (2) the same configuration on ONE GPU
         # and as N independent replicas (every rank the whole problem, no collective)
         step(0)
@@ -618,7 +626,7 @@ def main():
     kern = {}
     batched = None
     ab = synth.algorithmic_bytes(n, kmax)
-    if world > 1 and sharded is not None:
+    if world > 1 and sharded is not None and args.full:
         # every rank times its own launches (collective: the exchange needs all ranks); rank 0 reports the MAX over ranks
         from bluest_amd.plan import _stream
         lib, h = plan.lib, plan._h
@@ -674,7 +682,7 @@ def main():
                     "clocks": "this run, per GPU; one launch = kernel + dispatch gap to its successor",
                     "step": {"algorithmic_bytes_all_gpus": ab["eval"] * n_out, "achieved_GBps_all_gpus": ab["eval"] * n_out / sec_per_step / 1e9,
                              "frac_of_aggregate_peak": ab["eval"] * n_out / sec_per_step / (HBM_PEAK * world)}}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         from bluest_amd.plan import _stream
         lib, h = plan.lib, plan._h
         m = ring[0]
@@ -774,14 +782,16 @@ def main():
                        "n_models": n, "k_max": kmax, "K_tot": L, "n_out": n_out_all, "batch": 1, "parallelism": par,
                        "evaluation": "matrix-free (group inverses recomputed in registers, csrc/matfree.hip)" if plan.matfree else "stored group inverses",
                        "launch": stepper.launch_label()},
-            "kernels_us": kern,
+            "full": args.full,
         }
+        if args.full:
+            out["kernels_us"] = kern
         out.update(extra)
         if roofline is not None:
             out["roofline"] = roofline
         if batched is not None:
             out["batched"] = batched
-        if world == 1 and not args.no_sap:
+        if world == 1 and args.full and not args.no_sap:
             out["sap_wallclock"] = sap_wallclock(prob)
             if not args.no_cpu_baseline:
                 try:
@@ -790,7 +800,7 @@ def main():
                     out["sap_wallclock"]["setup_speedup_vs_cpu_baseline"] = cb_s["setup_s"] / out["sap_wallclock"]["warm"]["setup_s"]
                 except Exception as err:      # the headline line must not depend on this leg
                     out["sap_wallclock"]["cpu_baseline"] = {"error": repr(err)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(prob)
             out["cpu_baseline"] = cb
             out["speedup_vs_cpu_baseline"] = out["value"] / cb["value"]

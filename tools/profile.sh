@@ -3,7 +3,7 @@
 #   (1) rocprofv3 --kernel-trace --stats of the bench command (without the SAP / CPU / batched legs, so the trace holds the timed
 #       hot path), (2) separate --pmc passes for FETCH_SIZE and WRITE_SIZE (MI355X_MICROARCH.md, HBM section; the program directly
 #       after `--`), summarised by tools/pmc_traffic.py into <tag>_kernel_stats<suffix>.csv / <tag>_pmc_traffic<suffix>.json;
-# then (3) the default bench of every configuration (its line reads the summaries of (1)-(2): run profile.sh, copy the summaries to
+# then (3) the --full bench of every configuration (its line reads the summaries of (1)-(2): run profile.sh, copy the summaries to
 # profiles/, run it again for lines with frac_rocprof / traffic of the SAME build -- or accept the previous round's), (4) kernel
 # statistics of whole SAP solves, (5) the driver's command line, (6) master phases, step parts, quality sweep.
 # Summaries go to gpurun_out/profiles_<tag>/ (raw per-dispatch CSVs stay behind).     on the GPU box:  bash tools/profile.sh r04
@@ -22,9 +22,9 @@ for cfg in "20 5 8" "20 5 1" "12 12 1" "25 6 1" "25 6 1 stored"; do
   if [ "$4" = "stored" ]; then export BLUEST_MATFREE=0; SFX="_stored${SFX}"; else unset BLUEST_MATFREE; fi
   ARGS="--n $1 --kmax $2 --n-out $3"
   D=$OUT/cfg$SFX; mkdir -p $D
-  rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -- python bench.py $LEAN $ARGS > $D/bench_under_trace.json 2> $D/trace.err
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $D/pmc_fetch -- python bench.py $LEAN $ARGS --no-graph --steps 200 --warmup 20 > $D/bench_under_pmc_fetch.json 2> $D/pmc_fetch.err
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $D/pmc_write -- python bench.py $LEAN $ARGS --no-graph --steps 200 --warmup 20 > $D/bench_under_pmc_write.json 2> $D/pmc_write.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -- python bench.py --full $LEAN $ARGS > $D/bench_under_trace.json 2> $D/trace.err
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $D/pmc_fetch -- python bench.py --full $LEAN $ARGS --no-graph --steps 200 --warmup 20 > $D/bench_under_pmc_fetch.json 2> $D/pmc_fetch.err
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $D/pmc_write -- python bench.py --full $LEAN $ARGS --no-graph --steps 200 --warmup 20 > $D/bench_under_pmc_write.json 2> $D/pmc_write.err
   python tools/pmc_traffic.py $D $TAG $SUM "$SFX" > $SUM/summary$SFX.txt
   if [ -z "$SFX" ]; then
     cp "$(ls -t $D/trace/*/*_kernel_stats.csv | head -1)" $SUM/${TAG}_kernel_stats_full.csv
@@ -35,11 +35,11 @@ done
 unset BLUEST_MATFREE
 fi
 if [[ "$STAGE" == *B* ]]; then
-# (3) default bench lines
-python bench.py > $SUM/${TAG}_bench.json 2> $OUT/bench.err
-python bench.py --n 20 --kmax 5 --n-out 1 > $SUM/${TAG}_bench_n20_k5_o1.json 2> $OUT/bench_o1.err
-python bench.py --n 12 --kmax 12 --n-out 1 > $SUM/${TAG}_bench_n12_k12_o1.json 2> $OUT/bench_n12.err
-python bench.py --n 25 --kmax 6 --n-out 1 > $SUM/${TAG}_bench_n25_k6_o1.json 2> $OUT/bench_n25.err
+# (3) --full bench lines (kernel times, roofline, batched, SAP wall-clock, CPU baselines)
+python bench.py --full > $SUM/${TAG}_bench.json 2> $OUT/bench.err
+python bench.py --full --n 20 --kmax 5 --n-out 1 > $SUM/${TAG}_bench_n20_k5_o1.json 2> $OUT/bench_o1.err
+python bench.py --full --n 12 --kmax 12 --n-out 1 > $SUM/${TAG}_bench_n12_k12_o1.json 2> $OUT/bench_n12.err
+python bench.py --full --n 25 --kmax 6 --n-out 1 > $SUM/${TAG}_bench_n25_k6_o1.json 2> $OUT/bench_n25.err
 # (5) the driver's command line, verbatim
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $SUM/${TAG}_bench_driver_style.json 2> $OUT/bench_driver.err
 echo "bench lines done"
