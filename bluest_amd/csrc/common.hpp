@@ -14,12 +14,17 @@
 #include <atomic>
 #include <chrono>
 #include <mutex>
+#include <type_traits>
 
 #include "bluest_hip.h"
 
 // ---- error plumbing (definitions in runtime.hip) -----------------------------------------------------
 int fail(int code, const char *fmt, ...);
 int require_gpu();
+
+// compute units and per-workgroup LDS limit of HIP device `dev`, queried once per device (thread-safe; runtime.hip)
+struct DeviceProps { int cus; size_t lds_per_wg; };
+hipError_t device_props(int dev, DeviceProps *out);
 
 #define HIP_TRY(expr)                                                                                        \
     do {                                                                                                     \

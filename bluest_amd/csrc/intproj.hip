@@ -45,10 +45,10 @@ extern "C" int bluest_intproj_eval(int N, int n_out, int LL, const double *base_
     if (LL <= 0 || LL > 32) return fail(BLUEST_ERR_ARG, "LL=%d out of range (1..32)", LL);
     if (n_cand <= 0 || n_cand > 0x7fffffffLL) return fail(BLUEST_ERR_ARG, "n_cand out of range");
     if (!base_dev || !cols_dev || !ms_dev || !V_dev) return fail(BLUEST_ERR_ARG, "null pointer");
-#define LIP(NT) hipLaunchKernelGGL((k_intproj<NT>), dim3((unsigned)n_cand, n_out), dim3(64), 0, (hipStream_t)stream, N, n_out, LL, \
-                                   base_dev, cols_dev, ms_dev, n_cand, V_dev)
-    NT_DISPATCH(N, LIP);
-#undef LIP
+    nt_dispatch(N, [&](auto nt) {
+        hipLaunchKernelGGL((k_intproj<decltype(nt)::value>), dim3((unsigned)n_cand, n_out), dim3(64), 0, (hipStream_t)stream, N, n_out, LL,
+                           base_dev, cols_dev, ms_dev, n_cand, V_dev);
+    });
     HIP_TRY(hipGetLastError());
     return BLUEST_OK;
 }

@@ -47,9 +47,11 @@ struct MfState {           // hangs off bluest_plan_s::mf
     double *d_amax = nullptr;                  // [n_out][wgs][N + 1]: model-wise max |m|, then their maximum
     double *d_rec = nullptr;                   // [n_out][N*N + 2N + 1]  (evaluations that never leave this GPU)
     int32_t *d_flag = nullptr;                 // k_mf_check: number of blocks that are not safely positive definite
+    int32_t *d_wg_begin = nullptr;             // [n_out + 1] first workgroup of every output in k_solve_grad_mf
     std::vector<int32_t> tile_begin;           // host copy
     int wgs = 0, nw = 8, nsym = 0;
-    int64_t n_tiles = 0;
+    int wgs_grad = 0, bpo = 0;                 // k_solve_grad_mf: workgroups, and workgroups per output when equal for all (else 0)
+    int64_t most = 0;                          // tiles of the output with the most
     size_t lds_phi = 0, lds_grad = 0;
 };
 
@@ -489,7 +491,6 @@ void mf_release(bluest_plan_s *p)
     MfState *S = reinterpret_cast<MfState *>(p->mf);
     if (!S) return;
     if (S->blob) (void)pool_free(S->blob);
-    if (p->mf_wg_begin_dev) { (void)pool_free(p->mf_wg_begin_dev); p->mf_wg_begin_dev = nullptr; }
     delete S;
     p->mf = nullptr;
     p->matfree = false;
@@ -497,6 +498,15 @@ void mf_release(bluest_plan_s *p)
 }
 
 static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+static MfArgs mf_args(bluest_plan_t plan)
+{
+    MfState *S = reinterpret_cast<MfState *>(plan->mf);
+    MfArgs A;
+    A.N = plan->N; A.nsym = S->nsym; A.n_out = (int)plan->outs.size(); A.wgs = S->wgs; A.tiles = S->d_tiles; A.tile_begin = S->d_tile_begin;
+    A.C = S->d_C; A.groups = S->d_groups; A.map = S->d_map; A.goff = plan->d_goff;
+    return A;
+}
 
 // called at the end of bluest_plan_finalize.  Leaves plan->matfree = false (and no state) when the plan does not qualify.
 int mf_finalize(bluest_plan_t plan)
@@ -535,18 +545,20 @@ int mf_finalize(bluest_plan_t plan)
         }
     }
     S->tile_begin[n_out] = (int32_t)tiles.size();
-    S->n_tiles = (int64_t)tiles.size();
     // workgroups of the Phi pass per output: all compute units busy, a tile or more per wavefront
-    static int cus_of[64] = {0};           // (hipGetDeviceProperties costs tens of milliseconds: once per device)
-    const int dv = (plan->device >= 0 && plan->device < 64) ? plan->device : 0;
-    if (!cus_of[dv]) {
-        int c = 0;
-        cus_of[dv] = (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, plan->device) == hipSuccess && c > 0) ? c : 256;
+    DeviceProps dp;
+    const int cus = (device_props(plan->device, &dp) == hipSuccess && dp.cus > 0) ? dp.cus : 256;
+    for (int o = 0; o < n_out; o++) S->most = std::max<int64_t>(S->most, S->tile_begin[o + 1] - S->tile_begin[o]);
+    S->wgs = (int)std::max<int64_t>(1, std::min<int64_t>((cus + n_out - 1) / n_out, (S->most + S->nw - 1) / S->nw));
+    // workgroups of the solve + gradient pass per output: MF_TILE_WAVES tiles each
+    std::vector<int32_t> wg_begin((size_t)n_out + 1, 0);
+    for (int o = 0; o < n_out; o++) {
+        const int nt = S->tile_begin[o + 1] - S->tile_begin[o];
+        wg_begin[(size_t)o + 1] = wg_begin[(size_t)o] + std::max(1, (nt + MF_TILE_WAVES - 1) / MF_TILE_WAVES);
     }
-    const int cus = cus_of[dv];
-    int64_t most = 0;
-    for (int o = 0; o < n_out; o++) most = std::max<int64_t>(most, S->tile_begin[o + 1] - S->tile_begin[o]);
-    S->wgs = (int)std::max<int64_t>(1, std::min<int64_t>((cus + n_out - 1) / n_out, (most + S->nw - 1) / S->nw));
+    S->wgs_grad = wg_begin[(size_t)n_out];
+    S->bpo = wg_begin[1];
+    for (int o = 0; o < n_out; o++) if (wg_begin[(size_t)o + 1] - wg_begin[(size_t)o] != wg_begin[1]) S->bpo = 0;
     // mappings (identity plans need none)
     std::vector<int32_t> map;
     if (!plan->identity) {
@@ -568,9 +580,10 @@ int mf_finalize(bluest_plan_t plan)
     const size_t b_pk = al((size_t)pk_words * 8);
     const size_t b_tiles = al(tiles.size() * sizeof(MfTile)), b_tb = al((n_out + 1) * sizeof(int32_t)), b_C = al((size_t)n_out * N * N * 8),
                  b_gp = al(n_out * sizeof(void *)), b_map = al(map.size() * sizeof(int32_t)), b_part = al((size_t)n_out * S->wgs * S->nsym * sizeof(double)),
-                 b_amax = al((size_t)n_out * S->wgs * (N + 1) * 8), b_rec = al((size_t)n_out * reclen * 8), b_flag = al(sizeof(int32_t));
-    const size_t total = b_tiles + b_tb + b_C + b_gp + b_map + b_part + b_amax + b_rec + b_flag + b_pk;
-    DeviceScopeN scope(plan->device);
+                 b_amax = al((size_t)n_out * S->wgs * (N + 1) * 8), b_rec = al((size_t)n_out * reclen * 8), b_flag = al(sizeof(int32_t)),
+                 b_wb = al((n_out + 1) * sizeof(int32_t));
+    const size_t total = b_tiles + b_tb + b_C + b_gp + b_map + b_part + b_amax + b_rec + b_flag + b_wb + b_pk;
+    DeviceScope scope(plan->device);
     hipError_t e = pool_alloc(&S->blob, total);
     if (e != hipSuccess) { delete S; HIP_TRY(e); }
     unsigned char *d = reinterpret_cast<unsigned char *>(S->blob);
@@ -583,6 +596,7 @@ int mf_finalize(bluest_plan_t plan)
     S->d_amax = reinterpret_cast<double *>(d); d += b_amax;
     S->d_rec = reinterpret_cast<double *>(d); d += b_rec;
     S->d_flag = reinterpret_cast<int32_t *>(d); d += b_flag;
+    S->d_wg_begin = reinterpret_cast<int32_t *>(d); d += b_wb;
     S->d_packed = reinterpret_cast<uint64_t *>(d);
     plan->mf = S;
     std::vector<const uint64_t *> gp((size_t)n_out);
@@ -599,6 +613,7 @@ int mf_finalize(bluest_plan_t plan)
     }
     hipError_t err = hipMemcpy(S->d_tiles, tiles.data(), tiles.size() * sizeof(MfTile), hipMemcpyHostToDevice);
     if (err == hipSuccess) err = hipMemcpy(S->d_tile_begin, S->tile_begin.data(), (n_out + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(S->d_wg_begin, wg_begin.data(), (n_out + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
     if (err == hipSuccess) err = hipMemcpy((void *)S->d_groups, gp.data(), n_out * sizeof(void *), hipMemcpyHostToDevice);
     if (err == hipSuccess && !map.empty()) err = hipMemcpy(S->d_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     for (int o = 0; o < n_out && err == hipSuccess; o++)
@@ -608,10 +623,8 @@ int mf_finalize(bluest_plan_t plan)
     S->lds_phi = ((size_t)N * N + (size_t)S->nw * S->nsym + (size_t)S->nw * N) * 8;
     S->lds_grad = (size_t)N * N * 8;
     // every block safely positive definite?
-    MfArgs A;
-    A.N = N; A.nsym = S->nsym; A.n_out = n_out; A.wgs = S->wgs; A.tiles = S->d_tiles; A.tile_begin = S->d_tile_begin; A.C = S->d_C;
-    A.groups = S->d_groups; A.map = S->d_map; A.goff = plan->d_goff;
-    const int cgrid = (int)std::max<int64_t>(1, std::min<int64_t>(256, (most + 3) / 4));
+    const MfArgs A = mf_args(plan);
+    const int cgrid = (int)std::max<int64_t>(1, std::min<int64_t>(256, (S->most + 3) / 4));
     hipLaunchKernelGGL(k_mf_check, dim3(cgrid, n_out), dim3(256), (size_t)N * N * 8, 0, A, S->d_flag);
     int32_t flag = 1;
     err = hipMemcpy(&flag, S->d_flag, sizeof(int32_t), hipMemcpyDeviceToHost);
@@ -625,15 +638,6 @@ int mf_finalize(bluest_plan_t plan)
     plan->mf_gradient = true;
     plan->matfree = full;
     return BLUEST_OK;
-}
-
-static MfArgs mf_args(bluest_plan_t plan)
-{
-    MfState *S = reinterpret_cast<MfState *>(plan->mf);
-    MfArgs A;
-    A.N = plan->N; A.nsym = S->nsym; A.n_out = (int)plan->outs.size(); A.wgs = S->wgs; A.tiles = S->d_tiles; A.tile_begin = S->d_tile_begin;
-    A.C = S->d_C; A.groups = S->d_groups; A.map = S->d_map; A.goff = plan->d_goff;
-    return A;
 }
 
 // Phi record of ONE allocation vector into rec_dev (NULL: the plan's own record buffer, returned through *rec_used)
@@ -660,29 +664,11 @@ int mf_solve_grad(bluest_plan_t plan, const double *rec_dev, double delta, doubl
     MfState *S = reinterpret_cast<MfState *>(plan->mf);
     if (!S) return fail(BLUEST_ERR_STATE, "matrix-free state missing");
     const MfArgs A = mf_args(plan);
-    // workgroups per output: MF_TILE_WAVES tiles each; the table of first workgroups rides in the (host-built) tile_begin pattern
-    if (!plan->mf_wg_begin_dev) {
-        std::vector<int32_t> wb((size_t)A.n_out + 1, 0);
-        for (int o = 0; o < A.n_out; o++) {
-            const int nt = S->tile_begin[o + 1] - S->tile_begin[o];
-            wb[(size_t)o + 1] = wb[(size_t)o] + std::max(1, (nt + MF_TILE_WAVES - 1) / MF_TILE_WAVES);
-        }
-        DeviceScopeN scope(plan->device);
-        HIP_TRY(pool_alloc((void **)&plan->mf_wg_begin_dev, al((A.n_out + 1) * sizeof(int32_t))));
-        HIP_TRY(hipMemcpy(plan->mf_wg_begin_dev, wb.data(), (A.n_out + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-        plan->mf_wgs_grad = wb[(size_t)A.n_out];
-        plan->mf_bpo = wb[1];
-        for (int o = 0; o < A.n_out; o++) if (wb[(size_t)o + 1] - wb[(size_t)o] != wb[1]) plan->mf_bpo = 0;
-    }
-    const dim3 grid((unsigned)plan->mf_wgs_grad);
-    int kmax = 0;
-    for (const auto &od : plan->outs) kmax = std::max(kmax, od.K);
-#define LMF2(NT, KU) hipLaunchKernelGGL((k_solve_grad_mf<NT, KU>), grid, dim3(64 * (MF_TILE_WAVES + 1)), S->lds_grad, st, A, rec_dev, delta, \
-                                        plan->d_rows, plan->fold_reg, plan->d_partial, (const int32_t *)plan->mf_wg_begin_dev, plan->mf_bpo, var_dev, plan->d_v, status_dev, grad_dev, ma)
-#define LMF(NT) do { if (kmax <= 5) LMF2(NT, 5); else if (kmax <= 6) LMF2(NT, 6); else LMF2(NT, 8); } while (0)
-    NT_DISPATCH(plan->N, LMF);
-#undef LMF
-#undef LMF2
+    const dim3 grid((unsigned)S->wgs_grad);
+    nt_dispatch(plan->N, [&](auto nt) { dispatch_le<5, 6, 8>(plan->kmax, [&](auto ku) {
+        hipLaunchKernelGGL((k_solve_grad_mf<decltype(nt)::value, decltype(ku)::value>), grid, dim3(64 * (MF_TILE_WAVES + 1)), S->lds_grad, st, A,
+                           rec_dev, delta, plan->d_rows, plan->fold_reg, plan->d_partial, S->d_wg_begin, S->bpo, var_dev, plan->d_v, status_dev, grad_dev, ma);
+    }); });
     HIP_TRY(hipGetLastError());
     return BLUEST_OK;
 }
@@ -712,9 +698,7 @@ int mf_grad(bluest_plan_t plan, const double *v_dev, const int32_t *status_dev, 
     MfState *S = reinterpret_cast<MfState *>(plan->mf);
     if (!S) return fail(BLUEST_ERR_STATE, "matrix-free state missing");
     const MfArgs A = mf_args(plan);
-    int64_t most = 0;
-    for (int o = 0; o < A.n_out; o++) most = std::max<int64_t>(most, S->tile_begin[o + 1] - S->tile_begin[o]);
-    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((most + 3) / 4, 1024 / std::max(1, A.n_out)));
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((S->most + 3) / 4, 1024 / std::max(1, A.n_out)));
     hipLaunchKernelGGL(k_grad_mf, dim3(gx, (unsigned)A.n_out), dim3(256), (size_t)(A.N * A.N + A.N) * 8, st, A, v_dev, status_dev, grad_dev);
     HIP_TRY(hipGetLastError());
     return BLUEST_OK;

@@ -1377,24 +1377,18 @@ __global__ __launch_bounds__(256) void k_price(int64_t L, int n_out, const doubl
 // ------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------
-static int master_lds_limit()
+static int master_lds_limit(int dev)
 {
-    static int limit_of[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 64 << 10;
-    if (!limit_of[dev]) {
-        hipDeviceProp_t prop;
-        limit_of[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess) ? (int)std::min<size_t>(prop.sharedMemPerBlock, 160u << 10) : (64 << 10);
-    }
-    return limit_of[dev];
+    DeviceProps dp;
+    return device_props(dev, &dp) == hipSuccess ? (int)std::min<size_t>(dp.lds_per_wg, 160u << 10) : (64 << 10);
 }
 
 // Which instantiation runs a problem, and the largest support it holds.  Up to 32 models the register tiles 12 / 20 / 26 / 32.
 // Beyond: 40 / 48 / 64 in registers (one evaluation's elimination 3 us instead of 150 in LDS) when the larger Phi stride (nt + 2
 // instead of N + 1) still leaves the support the natural layout would allow, or N + 16 entries; else the LDS eliminations (nt = 0).
-static int master_choose_nt(int N, int n_out, int KM, int *s_max)
+static int master_choose_nt(int dev, int N, int n_out, int KM, int *s_max)
 {
-    const size_t limit = (size_t)master_lds_limit() - MASTER_STATIC_LDS;
+    const size_t limit = (size_t)master_lds_limit(dev) - MASTER_STATIC_LDS;
     auto fit = [&](int nt) {
         int S = MASTER_SMAX;
         while (S > 0 && master_lds_bytes(N, n_out, S, KM, nt) > limit) S -= 2;
@@ -1416,10 +1410,7 @@ extern "C" int bluest_master_max_support(bluest_plan_t plan, int *s_max)
     if (!plan || !s_max) return fail(BLUEST_ERR_ARG, "null pointer");
     if (!plan->finalized) return fail(BLUEST_ERR_STATE, "plan not finalized");
     int rc = require_gpu(); if (rc) return rc;
-    int KM = 0;
-    for (const auto &od : plan->outs) KM = std::max(KM, od.K);
-    const int n_out = (int)plan->outs.size();
-    (void)master_choose_nt(plan->N, n_out, KM, s_max);     // 0: this problem does not fit the single-workgroup master
+    (void)master_choose_nt(plan->device, plan->N, (int)plan->outs.size(), plan->kmax, s_max);     // 0: this problem does not fit the single-workgroup master
     return BLUEST_OK;
 }
 
@@ -1494,9 +1485,10 @@ static int master_launch(bluest_plan_t plan, int S, const int64_t *support_host,
         if (!found) return fail(BLUEST_ERR_ARG, "group %lld belongs to no output", (long long)gi);
         KM = std::max(KM, kk[j]);
     }
-    const int nt = master_choose_nt(N, n_out, KM, nullptr);
+    const int nt = master_choose_nt(plan->device, N, n_out, KM, nullptr);
     const size_t lds = master_lds_bytes(N, n_out, S, KM, nt);
-    if (lds > (size_t)master_lds_limit() - MASTER_STATIC_LDS) return fail(BLUEST_ERR_ARG, "master problem needs %zu bytes of LDS (limit %d)", lds, master_lds_limit() - MASTER_STATIC_LDS);
+    const int lds_limit = master_lds_limit(plan->device) - MASTER_STATIC_LDS;
+    if (lds > (size_t)lds_limit) return fail(BLUEST_ERR_ARG, "master problem needs %zu bytes of LDS (limit %d)", lds, lds_limit);
     idx.assign((size_t)S * KM, 0);
     for (int j = 0; j < S; j++) for (int l = 0; l < kk[j]; l++) idx[(size_t)j * KM + l] = (uint8_t)members[j][l];
     // one descriptor blob: [invcov pointers][boff][cc][kk][idx]
@@ -1517,7 +1509,7 @@ static int master_launch(bluest_plan_t plan, int S, const int64_t *support_host,
         memcpy(h + b_ptr + b_off + b_cc + b_kk + b_idx, cap_model_host, (size_t)ncap * sizeof(int32_t));
         memcpy(h + b_ptr + b_off + b_cc + b_kk + b_idx + b_cm, cap_b_host, b_cb);
     }
-    DeviceScopeN scope(plan->device);
+    DeviceScope scope(plan->device);
     if (plan->master_bytes < total) {
         // from the library's block cache (plan.hip): a hipMalloc here cost every NEW problem's first master launch 0.1-0.3 ms
         if (plan->d_master) { (void)hipStreamSynchronize((hipStream_t)stream); (void)pool_free(plan->d_master); plan->d_master = nullptr; }

@@ -370,7 +370,7 @@ __global__ __launch_bounds__(256) void k_grad_tiles(const TileDesc *__restrict__
 // tiles per workgroup of the fused kernel: wavefront 0 solves, wavefronts 1..TPB own one tile each.  15 (1024 threads,
 // 128 VGPRs) while the register-resident matrix (2 NT VGPRs) and tile (KU (KU+1) + KU VGPRs) fit, else 7 (512 threads, 256 VGPRs)
 __host__ __device__ constexpr int fused_tpb(int NT, int KU) { return (NT <= 26 && KU <= 8) ? 15 : 7; }
-static int pick_ku(int kmax) { return kmax <= 5 ? 5 : kmax <= 6 ? 6 : kmax <= 8 ? 8 : 12; }
+template <class F> static void solve_grad_ku_dispatch(int kmax, F &&launch) { dispatch_le<5, 6, 8, 12>(kmax, launch); }   // KU of k_solve_grad
 template <int NT, int KU>
 __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int N, int n_out, const RowDesc *__restrict__ rows, int nsym, FoldReg reg,
                                                     const double2 *__restrict__ partial, const double *__restrict__ rec, double delta,
@@ -595,7 +595,12 @@ hipError_t pool_free(void *p, bool recycle)
     return hipFree(p);
 }
 
-typedef DeviceScopeN DeviceScope;      // plan.hpp
+static void output_release(OutputDesc &od)
+{
+    if (od.d_invcov) (void)pool_free(od.d_invcov);
+    if (od.d_groups && od.owns_groups) (void)pool_free(od.d_groups);
+    od.d_invcov = nullptr; od.d_groups = nullptr;
+}
 
 static void plan_free_device(bluest_plan_s *p)
 {
@@ -605,11 +610,7 @@ static void plan_free_device(bluest_plan_s *p)
     if (p->d_master) (void)pool_free(p->d_master);
     p->d_arena = p->d_scratch = p->d_master = nullptr;
     p->master_bytes = 0;
-    for (auto &od : p->outs) {
-        if (od.d_invcov) (void)pool_free(od.d_invcov);
-        if (od.d_groups && od.owns_groups) (void)pool_free(od.d_groups);
-        od.d_invcov = nullptr; od.d_groups = nullptr;
-    }
+    for (auto &od : p->outs) output_release(od);
 }
 
 extern "C" int bluest_plan_create(bluest_plan_t *plan, int n_models, int64_t L_global)
@@ -726,13 +727,6 @@ static int output_to_device(bluest_plan_t plan, OutputDesc &od)
         HIP_TRY(hipMemcpy(od.d_groups, narrow.data(), (size_t)ng, hipMemcpyHostToDevice));
     }
     return BLUEST_OK;
-}
-
-static void output_release(OutputDesc &od)
-{
-    if (od.d_invcov) (void)pool_free(od.d_invcov);
-    if (od.d_groups && od.owns_groups) (void)pool_free(od.d_groups);
-    od.d_invcov = nullptr; od.d_groups = nullptr;
 }
 
 extern "C" int bluest_plan_add_output(bluest_plan_t plan, int K, const int64_t *sizes, const int64_t *groups,
@@ -915,18 +909,11 @@ struct RawArray {
     const T *data() const { return p.get(); }
     size_t size() const { return n; }
 };
-template <typename T>
-static int upload(Arena &arena, size_t off, T **dst, const RawArray<T> &src)
+template <typename T, class Host>      // Host: std::vector<T> or RawArray<T>
+static int upload(Arena &arena, size_t off, T **dst, const Host &src)
 {
     *dst = reinterpret_cast<T *>(arena.base + off);
     if (src.size()) HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return BLUEST_OK;
-}
-template <typename T>
-static int upload(Arena &arena, size_t off, T **dst, const std::vector<T> &src)
-{
-    *dst = reinterpret_cast<T *>(arena.base + off);
-    if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return BLUEST_OK;
 }
 
@@ -948,76 +935,70 @@ static void parallel_items(int n_items, F fn)
     for (auto &w : workers) w.join();
 }
 
-extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
-{
-    if (!plan) return fail(BLUEST_ERR_ARG, "plan is NULL");
-    if (plan->finalized) return fail(BLUEST_ERR_STATE, "plan already finalized");
-    if (plan->outs.empty()) return fail(BLUEST_ERR_STATE, "plan has no outputs");
-    if (max_candidates <= 0 || max_candidates > 65535) return fail(BLUEST_ERR_ARG, "max_candidates=%d out of range", max_candidates);
-    const int N = plan->N, n_out = (int)plan->outs.size();
-    const int nsym = N * (N + 1) / 2;
-    auto tri = [N](int a, int b) { return a * N - a * (a - 1) / 2 + (b - a); };
-    PhaseTimer timer("plan_finalize");
+// position of the packed-symmetric pair (a, b), a <= b, among the N (N + 1) / 2 rows of the Phi layout
+static inline int sym_row(int N, int a, int b) { return a * N - a * (a - 1) / 2 + (b - a); }
 
-    plan->nsym = nsym;
-    plan->shared = true;
-    for (int o = 1; o < n_out; o++) {
-        const OutputDesc &x = plan->outs[0], &y = plan->outs[o];
-        if (x.K != y.K || x.sizes != y.sizes || x.groups != y.groups || x.mapping != y.mapping) { plan->shared = false; break; }
-    }
-    // distinct STRUCTURES: with identical group lists and mappings every output has the same rows, chunks and slots, so the
-    // counting sort below runs once and the other outputs reuse its result shifted by their chunk base
-    const int n_struct = plan->shared ? 1 : n_out;
-
-    // ---- gradient pass: group-major tiles (descriptors only; values are scattered on the device) ----------------
-    {
-        int kmax_all = 0;
-        for (const auto &od : plan->outs) kmax_all = std::max(kmax_all, od.K);
-        // tiles per workgroup of the fused kernel.  What bounds its tile stream is the rate at which ONE compute unit pulls bytes
-        // that miss its L2 (~30 GB/s), so the tiles are spread over as many compute units as the device has (one workgroup of
-        // 1024 threads fills a compute unit's registers): 184 workgroups of 15 tiles left 72 of 256 units idle at the headline size
-        const int tpb_max = fused_tpb(pick_nt(N), pick_ku(kmax_all));
-        int64_t tiles_max = 1;
-        for (const auto &od : plan->outs) {
-            int64_t t = 0;
-            for (int k = 1; k <= od.K; k++) t += (od.sizes[k - 1] + 63) / 64;
-            tiles_max = std::max(tiles_max, t);
-        }
-        static std::atomic<int> cu_of[64];            // compute units per device (hipGetDeviceProperties costs about a millisecond)
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        int ncu = (dev >= 0 && dev < 64) ? cu_of[dev].load() : 0;
-        if (ncu <= 0) {
-            hipDeviceProp_t prop;
-            HIP_TRY(hipGetDeviceProperties(&prop, dev));
-            ncu = std::max(1, prop.multiProcessorCount);
-            if (dev >= 0 && dev < 64) cu_of[dev].store(ncu);
-        }
-        const int64_t wg_per_output = std::max<int64_t>(1, ncu / n_out);
-        const int64_t tpb_cu = std::max<int64_t>(1, (tiles_max + wg_per_output - 1) / wg_per_output);
-        plan->fused_tpb = (int)std::min<int64_t>(tpb_max, tpb_cu);
-    }
-    std::vector<TileDesc> tiles;
-    std::vector<std::vector<int64_t>> bucket_val(n_out);    // first tile of size bucket k: offset
+// what the steps of bluest_plan_finalize hand to one another (host side; the plan keeps only what its launches read)
+struct PlanLayout {
+    int n_struct;                                       // distinct group structures (1 when the outputs share theirs)
+    std::vector<TileDesc> tiles;                        // gradient pass
+    std::vector<std::vector<int64_t>> bucket_val;      // [output][k]: first tile value of size bucket k
     size_t n_tvals = 0;
+    int64_t CH = 256;                                   // Phi pass: entries per chunk of the destination-major symmetric CSR
+    std::vector<RowDesc> rows;
+    std::vector<int64_t> out_chunk_begin;               // n_out + 1: first chunk of every output (its partials are contiguous)
+    std::vector<int64_t> struct_entries, struct_slots;  // n_struct + 1: first entry / slot of every structure
+    RawArray<int32_t> perm, cols;                       // entry -> slot, slot -> column (per structure)
+    std::vector<int32_t> pslot;                         // regular rows (FoldReg)
+    std::vector<uint16_t> rank_ab;
+    std::vector<int32_t> invmap;                        // combine_grad
+    int32_t *d_perm = nullptr;                          // device copy of perm (inside the arena)
+    PlanLayout(int n_out, int nsym, int n_struct_)
+        : n_struct(n_struct_), bucket_val(n_out), rows((size_t)n_out * nsym), out_chunk_begin(n_out + 1, 0),
+          struct_entries(n_struct_ + 1, 0), struct_slots(n_struct_ + 1, 0) {}
+};
+
+// gradient pass: group-major tiles (descriptors only; values are scattered on the device), and the fused kernel's shape
+static int layout_tiles(bluest_plan_t plan, PlanLayout &lay)
+{
+    const int n_out = (int)plan->outs.size();
+    plan->kmax = 0;
+    for (const auto &od : plan->outs) plan->kmax = std::max(plan->kmax, od.K);
+    // tiles per workgroup of the fused kernel.  What bounds its tile stream is the rate at which ONE compute unit pulls bytes
+    // that miss its L2 (~30 GB/s), so the tiles are spread over as many compute units as the device has (one workgroup of
+    // 1024 threads fills a compute unit's registers): 184 workgroups of 15 tiles left 72 of 256 units idle at the headline size
+    int tpb_max = 0;
+    solve_grad_ku_dispatch(plan->kmax, [&](auto ku) { tpb_max = fused_tpb(pick_nt(plan->N), ku); });
+    int64_t tiles_max = 1;
+    for (const auto &od : plan->outs) {
+        int64_t t = 0;
+        for (int k = 1; k <= od.K; k++) t += (od.sizes[k - 1] + 63) / 64;
+        tiles_max = std::max(tiles_max, t);
+    }
+    DeviceProps dp;
+    HIP_TRY(device_props(plan->device, &dp));
+    const int64_t wg_per_output = std::max<int64_t>(1, dp.cus / n_out);
+    const int64_t tpb_cu = std::max<int64_t>(1, (tiles_max + wg_per_output - 1) / wg_per_output);
+    plan->fused_tpb = (int)std::min<int64_t>(tpb_max, tpb_cu);
+    std::vector<TileDesc> &tiles = lay.tiles;
     plan->grad_off.assign(n_out, 0);
     int64_t grad_len = 0;
     for (int o = 0; o < n_out; o++) {
         const OutputDesc &od = plan->outs[o];
         plan->grad_off[o] = grad_len;
         const size_t first_tile_of_output = tiles.size();
-        bucket_val[o].assign(od.K + 1, 0);
+        lay.bucket_val[o].assign(od.K + 1, 0);
         int64_t li = 0;
         for (int k = 1; k <= od.K; k++) {
             const int64_t Lk = od.sizes[k - 1];
-            bucket_val[o][k] = (int64_t)n_tvals;
+            lay.bucket_val[o][k] = (int64_t)lay.n_tvals;
             for (int64_t t0 = 0; t0 < Lk; t0 += 64) {
                 TileDesc td;
-                td.val_off = (int64_t)n_tvals;
+                td.val_off = (int64_t)lay.n_tvals;
                 td.grad_off = grad_len + li + t0;
                 td.n_valid = (int32_t)std::min<int64_t>(64, Lk - t0);
                 td.k = (int16_t)k; td.out = (int16_t)o;
-                n_tvals += (size_t)tile_slots(k) * 64;
+                lay.n_tvals += (size_t)tile_slots(k) * 64;
                 tiles.push_back(td);
             }
             li += Lk;
@@ -1036,181 +1017,178 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
         else if (plan->fused_bpo != bpo) plan->fused_bpo = 0;
         grad_len += od.L_o;
     }
-    n_tvals = std::max<size_t>(n_tvals, 128);       // the empty padding tiles read (and ignore) one slot pair at offset 0
+    lay.n_tvals = std::max<size_t>(lay.n_tvals, 128);       // the empty padding tiles read (and ignore) one slot pair at offset 0
     plan->grad_len = grad_len;
+    plan->n_tiles = (int64_t)tiles.size();
+    plan->spg_small = plan->L <= 4096 && plan->n_tiles <= 1024;
+    return BLUEST_OK;
+}
 
-    plan->identity = plan->shared && plan->outs[0].L_o == plan->L;
-    for (int64_t li = 0; plan->identity && li < plan->L; li++) plan->identity = plan->outs[0].mapping[li] == li;
-    // ---- Phi pass: destination-major symmetric CSR, positions only ---------------------------------------------------
+// Phi pass: destination-major symmetric CSR, positions only (counting sort of the entries by row, columns, row padding)
+static int layout_phi(bluest_plan_t plan, PlanLayout &lay, PhaseTimer &timer)
+{
+    const int N = plan->N, n_out = (int)plan->outs.size(), nsym = plan->nsym, n_struct = lay.n_struct;
     int iters = 1;
-    int64_t CH = 256, n_chunks = 0;
-    std::vector<RowDesc> rows((size_t)n_out * nsym);
-    std::vector<int32_t> out_row_begin(n_out + 1);
-    std::vector<int64_t> out_chunk_begin(n_out + 1, 0);
-    std::vector<int64_t> struct_entries(n_struct + 1, 0), struct_slots(n_struct + 1, 0);
-    RawArray<int32_t> perm, cols;
-    std::vector<int32_t> pslot;
-    plan->fold_reg = FoldReg{0, 0, nullptr};
-    std::vector<uint16_t> rank_ab;
-    plan->slots_per_output = 0;
-    {
-        // parallel counting sort: slice s of S owns a contiguous range of the output's groups; it counts its entries per row,
-        // the per-slice counts are prefix-summed into start offsets, then every slice writes the SLOT of its own entries -- rows
-        // keep their entries in group order whatever S is, so the layout (and every summation order on the GPU) is independent
-        // of threading
-        std::vector<std::vector<int64_t>> counts(n_struct, std::vector<int64_t>(nsym, 0));
-        int64_t max_row = 0;
-        // slices per structure: as many as there are threads for them, but no slice below ~250 k (j, l) pairs -- spawning and joining
-        // 16 threads costs more than counting the headline problem's 326 k pairs on one (the layout does not depend on S)
-        int64_t pairs0 = 0;
-        for (int k = 1; k <= plan->outs[0].K; k++) pairs0 += plan->outs[0].sizes[k - 1] * (int64_t)(k * (k + 1) / 2);
-        const int S = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads() / n_struct, pairs0 / 250000));
-        std::vector<std::vector<int64_t>> slice_cnt((size_t)n_struct * S, std::vector<int64_t>(nsym, 0));
-        auto for_groups_of_slice = [&](int o, int slice, auto &&body) {
-            const OutputDesc &od = plan->outs[o];
-            const int64_t lo = od.L_o * slice / S, hi = od.L_o * (slice + 1) / S;
-            int64_t go = 0, eo = 0, l0 = 0;
-            for (int k = 1; k <= od.K; k++) {
-                const int64_t Lk = od.sizes[k - 1];
-                const int ne = k * (k + 1) / 2;
-                for (int64_t i = std::max<int64_t>(lo - l0, 0); i < std::min<int64_t>(hi - l0, Lk); i++)
-                    body(k, od.groups.data() + go + i * k, eo + i * ne, l0 + i);
-                go += Lk * k; eo += Lk * ne; l0 += Lk;
-            }
-        };
-        parallel_items(n_struct * S, [&](int item) {
-            std::vector<int64_t> &cnt = slice_cnt[item];
-            for_groups_of_slice(item / S, item % S, [&](int k, const int64_t *g, int64_t, int64_t) {
-                for (int j = 0; j < k; j++)
-                    for (int l = j; l < k; l++) cnt[tri((int)std::min(g[j], g[l]), (int)std::max(g[j], g[l]))]++;
-            });
+    int64_t n_chunks = 0;
+    std::vector<RowDesc> &rows = lay.rows;
+    std::vector<int64_t> &out_chunk_begin = lay.out_chunk_begin, &struct_entries = lay.struct_entries, &struct_slots = lay.struct_slots;
+    // parallel counting sort: slice s of S owns a contiguous range of the output's groups; it counts its entries per row,
+    // the per-slice counts are prefix-summed into start offsets, then every slice writes the SLOT of its own entries -- rows
+    // keep their entries in group order whatever S is, so the layout (and every summation order on the GPU) is independent
+    // of threading
+    std::vector<std::vector<int64_t>> counts(n_struct, std::vector<int64_t>(nsym, 0));
+    int64_t max_row = 0;
+    // slices per structure: as many as there are threads for them, but no slice below ~250 k (j, l) pairs -- spawning and joining
+    // 16 threads costs more than counting the headline problem's 326 k pairs on one (the layout does not depend on S)
+    int64_t pairs0 = 0;
+    for (int k = 1; k <= plan->outs[0].K; k++) pairs0 += plan->outs[0].sizes[k - 1] * (int64_t)(k * (k + 1) / 2);
+    const int S = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads() / n_struct, pairs0 / 250000));
+    std::vector<std::vector<int64_t>> slice_cnt((size_t)n_struct * S, std::vector<int64_t>(nsym, 0));
+    auto for_groups_of_slice = [&](int o, int slice, auto &&body) {
+        const OutputDesc &od = plan->outs[o];
+        const int64_t lo = od.L_o * slice / S, hi = od.L_o * (slice + 1) / S;
+        int64_t go = 0, eo = 0, l0 = 0;
+        for (int k = 1; k <= od.K; k++) {
+            const int64_t Lk = od.sizes[k - 1];
+            const int ne = k * (k + 1) / 2;
+            for (int64_t i = std::max<int64_t>(lo - l0, 0); i < std::min<int64_t>(hi - l0, Lk); i++)
+                body(k, od.groups.data() + go + i * k, eo + i * ne, l0 + i);
+            go += Lk * k; eo += Lk * ne; l0 += Lk;
+        }
+    };
+    parallel_items(n_struct * S, [&](int item) {
+        std::vector<int64_t> &cnt = slice_cnt[item];
+        for_groups_of_slice(item / S, item % S, [&](int k, const int64_t *g, int64_t, int64_t) {
+            for (int j = 0; j < k; j++)
+                for (int l = j; l < k; l++) cnt[sym_row(N, (int)std::min(g[j], g[l]), (int)std::max(g[j], g[l]))]++;
         });
-        for (int o = 0; o < n_struct; o++)
-            for (int r = 0; r < nsym; r++) {
-                int64_t run = 0;
-                for (int sl = 0; sl < S; sl++) { const int64_t c = slice_cnt[(size_t)o * S + sl][r]; slice_cnt[(size_t)o * S + sl][r] = run; run += c; }
-                counts[o][r] = run;      // slice_cnt now holds each slice's start offset inside the row
-                max_row = std::max(max_row, run);
-            }
-        timer.lap("count");
-        while ((max_row + 256LL * iters - 1) / (256LL * iters) > 64 && iters < 1024) iters *= 2;
-        CH = 256LL * iters;
-        plan->iters = iters;
+    });
+    for (int o = 0; o < n_struct; o++)
+        for (int r = 0; r < nsym; r++) {
+            int64_t run = 0;
+            for (int sl = 0; sl < S; sl++) { const int64_t c = slice_cnt[(size_t)o * S + sl][r]; slice_cnt[(size_t)o * S + sl][r] = run; run += c; }
+            counts[o][r] = run;      // slice_cnt now holds each slice's start offset inside the row
+            max_row = std::max(max_row, run);
+        }
+    timer.lap("count");
+    while ((max_row + 256LL * iters - 1) / (256LL * iters) > 64 && iters < 1024) iters *= 2;
+    const int64_t CH = lay.CH = 256LL * iters;
+    plan->iters = iters;
 
-        for (int o = 0; o < n_out; o++) {
-            out_row_begin[o] = o * nsym;
-            out_chunk_begin[o] = n_chunks;
-            const std::vector<int64_t> &cnt = counts[plan->shared ? 0 : o];
+    for (int o = 0; o < n_out; o++) {
+        out_chunk_begin[o] = n_chunks;
+        const std::vector<int64_t> &cnt = counts[plan->shared ? 0 : o];
+        for (int a = 0; a < N; a++)
+            for (int b = a; b < N; b++) {
+                RowDesc &rd = rows[(size_t)o * nsym + sym_row(N, a, b)];
+                const int64_t nc = (cnt[sym_row(N, a, b)] + CH - 1) / CH;
+                rd.first_chunk = (int32_t)n_chunks;
+                rd.n_chunks = (int32_t)nc;
+                rd.out = (int16_t)o; rd.a = (int16_t)a; rd.b = (int16_t)b; rd.pad = 0;
+                n_chunks += nc;
+            }
+    }
+    out_chunk_begin[n_out] = n_chunks;
+    if (n_chunks <= 0 || n_chunks * CH > 0x7fffffff0LL) return fail(BLUEST_ERR_ARG, "problem too large for one plan (%lld chunks)", (long long)n_chunks);
+    plan->n_chunks = n_chunks;
+    // slot of every packed-symmetric entry (reference order: group-major, upper triangle row by row) and the column
+    // (= global index of the group) stored at that slot; per structure, relative to the structure's first chunk
+    for (int o = 0; o < n_struct; o++) {
+        int64_t ne_all = 0;
+        for (int k = 1; k <= plan->outs[o].K; k++) ne_all += plan->outs[o].sizes[k - 1] * (k * (k + 1) / 2);
+        struct_entries[o + 1] = struct_entries[o] + ne_all;
+        struct_slots[o + 1] = struct_slots[o] + (out_chunk_begin[o + 1] - out_chunk_begin[o]) * CH;
+    }
+    if (struct_slots[n_struct] > 0x7fffffffLL) return fail(BLUEST_ERR_ARG, "problem too large for one plan (%lld slots per structure set)", (long long)struct_slots[n_struct]);
+    lay.perm.reset((size_t)struct_entries[n_struct]);
+    lay.cols.reset((size_t)struct_slots[n_struct]);
+    parallel_items(n_struct * S, [&](int item) {
+        const int o = item / S;
+        std::vector<int64_t> &next = slice_cnt[item];     // start offsets, advanced as the slice writes
+        const OutputDesc &od = plan->outs[o];
+        const int64_t chunk0 = out_chunk_begin[o];
+        int32_t *pm = lay.perm.data() + struct_entries[o];
+        int32_t *cl = lay.cols.data() + struct_slots[o];
+        for_groups_of_slice(o, item % S, [&](int k, const int64_t *g, int64_t e0, int64_t li) {
+            int e = 0;
+            for (int j = 0; j < k; j++)
+                for (int l = j; l < k; l++, e++) {
+                    const int rr = sym_row(N, (int)std::min(g[j], g[l]), (int)std::max(g[j], g[l]));
+                    const int64_t pos = ((int64_t)rows[(size_t)o * nsym + rr].first_chunk - chunk0) * CH + next[rr]++;
+                    pm[e0 + e] = (int32_t)pos;
+                    cl[pos] = (int32_t)od.mapping[li];
+                }
+        });
+    });
+    // padding: value 0 (the device buffer is cleared), column = the row's first column (keeps max|m| per row exact, adds nothing)
+    parallel_items(n_struct, [&](int o) {
+        int32_t *cl = lay.cols.data() + struct_slots[o];
+        for (int rr = 0; rr < nsym; rr++) {
+            const RowDesc &rd = rows[(size_t)o * nsym + rr];
+            const int64_t beg = ((int64_t)rd.first_chunk - out_chunk_begin[o]) * CH, end = beg + (int64_t)rd.n_chunks * CH;
+            for (int64_t pos = beg + counts[o][rr]; pos < end; pos++) cl[pos] = cl[beg];
+        }
+    });
+    return BLUEST_OK;
+}
+
+// regular rows (solve.hpp FoldReg): fixed partial strides per destination class when that wastes at most a quarter
+static void layout_fold_reg(bluest_plan_t plan, PlanLayout &lay)
+{
+    const int N = plan->N, n_out = (int)plan->outs.size(), nsym = plan->nsym;
+    const int64_t n_chunks = plan->n_chunks;
+    plan->fold_reg = FoldReg{0, 0, nullptr};
+    plan->slots_per_output = 0;
+    int Cd = 0, Co = 0;
+    for (const RowDesc &rd : lay.rows) { if (rd.a == rd.b) Cd = std::max<int>(Cd, rd.n_chunks); else Co = std::max<int>(Co, rd.n_chunks); }
+    Co = std::max(Co, 1);
+    const int64_t slots = (int64_t)N * Cd + (int64_t)(nsym - N) * Co;
+    const bool no_reg = getenv("BLUEST_NO_REGULAR_FOLD") != nullptr;              // A/B switch, read per plan
+    if (!no_reg && Cd >= 1 && Cd <= 32 && Co <= 32 && slots * n_out * 4 <= n_chunks * 5 && slots < 0x7fffffff / std::max(1, n_out)) {
+        plan->fold_reg = FoldReg{Cd, Co, nullptr};
+        for (int a = 0; a < N; a++) lay.rank_ab.push_back((uint16_t)(a | (a << 8)));
+        for (int a = 0; a < N; a++) for (int b = a + 1; b < N; b++) lay.rank_ab.push_back((uint16_t)(a | (b << 8)));
+        plan->slots_per_output = (int)slots;
+        lay.pslot.assign((size_t)(plan->shared ? n_chunks / n_out : n_chunks), 0);
+        std::vector<int> off_before(N + 1, 0);          // pairs a' < b' with a' < a
+        for (int a = 0; a < N; a++) off_before[a + 1] = off_before[a] + (N - 1 - a);
+        for (int o = 0; o < lay.n_struct; o++)
             for (int a = 0; a < N; a++)
                 for (int b = a; b < N; b++) {
-                    RowDesc &rd = rows[(size_t)o * nsym + tri(a, b)];
-                    const int64_t nc = (cnt[tri(a, b)] + CH - 1) / CH;
-                    rd.first_chunk = (int32_t)n_chunks;
-                    rd.n_chunks = (int32_t)nc;
-                    rd.out = (int16_t)o; rd.a = (int16_t)a; rd.b = (int16_t)b; rd.pad = 0;
-                    n_chunks += nc;
+                    const RowDesc &rd = lay.rows[(size_t)o * nsym + sym_row(N, a, b)];
+                    const int64_t first = (a == b) ? (int64_t)a * Cd : (int64_t)N * Cd + (int64_t)(off_before[a] + (b - a - 1)) * Co;
+                    for (int j = 0; j < rd.n_chunks; j++)
+                        lay.pslot[(size_t)(rd.first_chunk - (plan->shared ? lay.out_chunk_begin[o] : 0)) + j] = (int32_t)(first + (plan->shared ? 0 : (int64_t)o * slots) + j);
                 }
-        }
-        out_row_begin[n_out] = n_out * nsym;
-        out_chunk_begin[n_out] = n_chunks;
-        if (n_chunks <= 0 || n_chunks * CH > 0x7fffffff0LL) return fail(BLUEST_ERR_ARG, "problem too large for one plan (%lld chunks)", (long long)n_chunks);
-        // slot of every packed-symmetric entry (reference order: group-major, upper triangle row by row) and the column
-        // (= global index of the group) stored at that slot; per structure, relative to the structure's first chunk
-        for (int o = 0; o < n_struct; o++) {
-            int64_t ne_all = 0;
-            for (int k = 1; k <= plan->outs[o].K; k++) ne_all += plan->outs[o].sizes[k - 1] * (k * (k + 1) / 2);
-            struct_entries[o + 1] = struct_entries[o] + ne_all;
-            struct_slots[o + 1] = struct_slots[o] + (out_chunk_begin[o + 1] - out_chunk_begin[o]) * CH;
-        }
-        if (struct_slots[n_struct] > 0x7fffffffLL) return fail(BLUEST_ERR_ARG, "problem too large for one plan (%lld slots per structure set)", (long long)struct_slots[n_struct]);
-        perm.reset((size_t)struct_entries[n_struct]);
-        cols.reset((size_t)struct_slots[n_struct]);
-        parallel_items(n_struct * S, [&](int item) {
-            const int o = item / S;
-            std::vector<int64_t> &next = slice_cnt[item];     // start offsets, advanced as the slice writes
-            const OutputDesc &od = plan->outs[o];
-            const int64_t chunk0 = out_chunk_begin[o];
-            int32_t *pm = perm.data() + struct_entries[o];
-            int32_t *cl = cols.data() + struct_slots[o];
-            for_groups_of_slice(o, item % S, [&](int k, const int64_t *g, int64_t e0, int64_t li) {
-                int e = 0;
-                for (int j = 0; j < k; j++)
-                    for (int l = j; l < k; l++, e++) {
-                        const int rr = tri((int)std::min(g[j], g[l]), (int)std::max(g[j], g[l]));
-                        const int64_t pos = ((int64_t)rows[(size_t)o * nsym + rr].first_chunk - chunk0) * CH + next[rr]++;
-                        pm[e0 + e] = (int32_t)pos;
-                        cl[pos] = (int32_t)od.mapping[li];
-                    }
-            });
-        });
-        // padding: value 0 (the device buffer is cleared), column = the row's first column (keeps max|m| per row exact, adds nothing)
-        parallel_items(n_struct, [&](int o) {
-            int32_t *cl = cols.data() + struct_slots[o];
-            for (int rr = 0; rr < nsym; rr++) {
-                const RowDesc &rd = rows[(size_t)o * nsym + rr];
-                const int64_t beg = ((int64_t)rd.first_chunk - out_chunk_begin[o]) * CH, end = beg + (int64_t)rd.n_chunks * CH;
-                for (int64_t pos = beg + counts[o][rr]; pos < end; pos++) cl[pos] = cl[beg];
-            }
-        });
-        // regular rows (solve.hpp FoldReg): fixed partial strides per destination class when that wastes at most a quarter
-        {
-            int Cd = 0, Co = 0;
-            for (const RowDesc &rd : rows) { if (rd.a == rd.b) Cd = std::max<int>(Cd, rd.n_chunks); else Co = std::max<int>(Co, rd.n_chunks); }
-            Co = std::max(Co, 1);
-            const int64_t slots = (int64_t)N * Cd + (int64_t)(nsym - N) * Co;
-            const bool no_reg = getenv("BLUEST_NO_REGULAR_FOLD") != nullptr;              // A/B switch, read per plan
-            if (!no_reg && Cd >= 1 && Cd <= 32 && Co <= 32 && slots * n_out * 4 <= n_chunks * 5 && slots < 0x7fffffff / std::max(1, n_out)) {
-                plan->fold_reg = FoldReg{Cd, Co, nullptr};
-                for (int a = 0; a < N; a++) rank_ab.push_back((uint16_t)(a | (a << 8)));
-                for (int a = 0; a < N; a++) for (int b = a + 1; b < N; b++) rank_ab.push_back((uint16_t)(a | (b << 8)));
-                plan->slots_per_output = (int)slots;
-                pslot.assign((size_t)(plan->shared ? n_chunks / n_out : n_chunks), 0);
-                std::vector<int> off_before(N + 1, 0);          // pairs a' < b' with a' < a
-                for (int a = 0; a < N; a++) off_before[a + 1] = off_before[a] + (N - 1 - a);
-                for (int o = 0; o < n_struct; o++)
-                    for (int a = 0; a < N; a++)
-                        for (int b = a; b < N; b++) {
-                            const RowDesc &rd = rows[(size_t)o * nsym + tri(a, b)];
-                            const int64_t first = (a == b) ? (int64_t)a * Cd : (int64_t)N * Cd + (int64_t)(off_before[a] + (b - a - 1)) * Co;
-                            for (int j = 0; j < rd.n_chunks; j++)
-                                pslot[(size_t)(rd.first_chunk - (plan->shared ? out_chunk_begin[o] : 0)) + j] = (int32_t)(first + (plan->shared ? 0 : (int64_t)o * slots) + j);
-                        }
-            }
-        }
-        timer.lap("CSR slots + columns");
     }
-    // ---- inverse maps for combine_grad ------------------------------------------------------------
-    std::vector<int32_t> invmap((size_t)n_out * plan->L, -1);
-    parallel_items(n_out, [&](int o) {
-        for (int64_t li = 0; li < plan->outs[o].L_o; li++) invmap[(size_t)o * plan->L + plan->outs[o].mapping[li]] = (int32_t)li;
-    });
-
-    plan->n_chunks = n_chunks;
-    plan->cols16 = plan->L <= 65536 && getenv("BLUEST_COLS32") == nullptr;       // (A/B switch: BLUEST_COLS32=1 keeps int32 columns)
     plan->partial_stride = plan->fold_reg.Cd > 0 ? (int64_t)plan->slots_per_output * n_out : n_chunks;
-    plan->n_rows = (int64_t)rows.size();
-    plan->n_tiles = (int64_t)tiles.size();
-    plan->max_cand = max_candidates;
-    plan->phi_bytes = n_chunks * CH * 8 + (plan->shared ? n_chunks / n_out : n_chunks) * CH * (plan->cols16 ? 2 : 4) + n_chunks * 16;
-    plan->grad_bytes = (int64_t)n_tvals * 8 + grad_len * 8;
-    {
-        const char *nt_env = getenv("BLUEST_TILE_NT");              // A/B switch, read per plan: 0 = plain loads
-        plan->tile_nt = nt_env ? atoi(nt_env) != 0 : true;
-    }
+}
 
-    timer.lap("tile descriptors + inverse maps");
+// inverse maps for combine_grad
+static void layout_invmap(bluest_plan_t plan, PlanLayout &lay)
+{
+    lay.invmap.assign(plan->outs.size() * plan->L, -1);
+    parallel_items((int)plan->outs.size(), [&](int o) {
+        for (int64_t li = 0; li < plan->outs[o].L_o; li++) lay.invmap[(size_t)o * plan->L + plan->outs[o].mapping[li]] = (int32_t)li;
+    });
+}
+
+// the plan's device arena: reserve every array, clear what the scatter leaves unwritten, upload the host-built tables
+static int arena_upload(bluest_plan_t plan, PlanLayout &lay)
+{
+    const int n_out = (int)plan->outs.size(), N = plan->N, max_candidates = plan->max_cand;
+    const int64_t n_chunks = plan->n_chunks, CH = lay.CH;
     int rc;
     if (plan->d_scratch) { (void)pool_free(plan->d_scratch); plan->d_scratch = nullptr; plan->scratch_bytes = 0; }
     Arena arena;
     const size_t o_vals = arena.reserve((size_t)n_chunks * CH * sizeof(double)), o_cols = arena.reserve((size_t)n_chunks * CH * sizeof(int32_t));
-    const size_t o_rows = arena.reserve(rows.size() * sizeof(RowDesc)), o_orb = arena.reserve(out_row_begin.size() * sizeof(int32_t));
-    const size_t o_tiles = arena.reserve(tiles.size() * sizeof(TileDesc)), o_tvals = arena.reserve(n_tvals * sizeof(double));
-    const size_t o_invmap = arena.reserve(invmap.size() * sizeof(int32_t));
+    const size_t o_rows = arena.reserve(lay.rows.size() * sizeof(RowDesc));
+    const size_t o_tiles = arena.reserve(lay.tiles.size() * sizeof(TileDesc)), o_tvals = arena.reserve(lay.n_tvals * sizeof(double));
+    const size_t o_invmap = arena.reserve(lay.invmap.size() * sizeof(int32_t));
     const size_t o_goff = arena.reserve(plan->grad_off.size() * sizeof(int64_t));
-    const size_t o_perm = arena.reserve(perm.size() * sizeof(int32_t));
-    const size_t o_ocb = arena.reserve(out_chunk_begin.size() * sizeof(int64_t));
+    const size_t o_perm = arena.reserve(lay.perm.size() * sizeof(int32_t));
     const size_t o_partial = arena.reserve((size_t)max_candidates * plan->partial_stride * sizeof(double2));
-    const size_t o_pslot = arena.reserve(pslot.size() * sizeof(int32_t)), o_rankab = arena.reserve(rank_ab.size() * sizeof(uint16_t));
+    const size_t o_pslot = arena.reserve(lay.pslot.size() * sizeof(int32_t)), o_rankab = arena.reserve(lay.rank_ab.size() * sizeof(uint16_t));
     const size_t o_v = arena.reserve((size_t)max_candidates * n_out * N * sizeof(double));
     const size_t o_status = arena.reserve((size_t)max_candidates * n_out * sizeof(int32_t));
     const size_t o_ticket = arena.reserve(256);
@@ -1219,42 +1197,42 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
     plan->d_vals = reinterpret_cast<double *>(arena.base + o_vals);
     plan->d_cols = reinterpret_cast<int32_t *>(arena.base + o_cols);
     plan->d_tvals = reinterpret_cast<double *>(arena.base + o_tvals);
-    int32_t *d_perm = nullptr;
+    plan->d_partial = reinterpret_cast<double2 *>(arena.base + o_partial);
+    plan->d_v = reinterpret_cast<double *>(arena.base + o_v);
+    plan->d_status = reinterpret_cast<int32_t *>(arena.base + o_status);
+    plan->d_ticket = reinterpret_cast<unsigned int *>(arena.base + o_ticket);
     // clear what the scatter kernels do not write (padding slots, padding lanes); then the small tables
     HIP_TRY(hipMemsetAsync(plan->d_vals, 0, (size_t)n_chunks * CH * sizeof(double), 0));
-    HIP_TRY(hipMemsetAsync(plan->d_tvals, 0, n_tvals * sizeof(double), 0));
+    HIP_TRY(hipMemsetAsync(plan->d_tvals, 0, lay.n_tvals * sizeof(double), 0));
     // columns: the structure's list sits at the structure's own chunk range (shared plans: output 0's range is the one the
     // Phi kernel reads; the other ranges stay unused)
+    const std::vector<int64_t> &ocb = lay.out_chunk_begin, &ss = lay.struct_slots;
     if (plan->cols16) {
-        RawArray<uint16_t> c16(cols.size());
-        for (size_t i = 0; i < cols.size(); i++) c16.data()[i] = (uint16_t)cols.data()[i];
+        RawArray<uint16_t> c16(lay.cols.size());
+        for (size_t i = 0; i < lay.cols.size(); i++) c16.data()[i] = (uint16_t)lay.cols.data()[i];
         uint16_t *d16 = reinterpret_cast<uint16_t *>(plan->d_cols);
-        for (int o = 0; o < n_struct; o++)
-            HIP_TRY(hipMemcpy(d16 + out_chunk_begin[o] * CH, c16.data() + struct_slots[o],
-                              (size_t)(struct_slots[o + 1] - struct_slots[o]) * sizeof(uint16_t), hipMemcpyHostToDevice));
+        for (int o = 0; o < lay.n_struct; o++)
+            HIP_TRY(hipMemcpy(d16 + ocb[o] * CH, c16.data() + ss[o], (size_t)(ss[o + 1] - ss[o]) * sizeof(uint16_t), hipMemcpyHostToDevice));
     } else
-    for (int o = 0; o < n_struct; o++)
-        HIP_TRY(hipMemcpy(plan->d_cols + out_chunk_begin[o] * CH, cols.data() + struct_slots[o],
-                          (size_t)(struct_slots[o + 1] - struct_slots[o]) * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((rc = upload(arena, o_rows, &plan->d_rows, rows))) return rc;
-    if ((rc = upload(arena, o_orb, &plan->d_out_row_begin, out_row_begin))) return rc;
-    if ((rc = upload(arena, o_tiles, &plan->d_tiles, tiles))) return rc;
-    if ((rc = upload(arena, o_invmap, &plan->d_invmap, invmap))) return rc;
+    for (int o = 0; o < lay.n_struct; o++)
+        HIP_TRY(hipMemcpy(plan->d_cols + ocb[o] * CH, lay.cols.data() + ss[o], (size_t)(ss[o + 1] - ss[o]) * sizeof(int32_t), hipMemcpyHostToDevice));
+    if ((rc = upload(arena, o_rows, &plan->d_rows, lay.rows))) return rc;
+    if ((rc = upload(arena, o_tiles, &plan->d_tiles, lay.tiles))) return rc;
+    if ((rc = upload(arena, o_invmap, &plan->d_invmap, lay.invmap))) return rc;
     if ((rc = upload(arena, o_goff, &plan->d_goff, plan->grad_off))) return rc;
-    if ((rc = upload(arena, o_perm, &d_perm, perm))) return rc;
-    if ((rc = upload(arena, o_ocb, &plan->d_out_chunk_begin, out_chunk_begin))) return rc;
-    if ((rc = upload(arena, o_pslot, &plan->d_pslot, pslot))) return rc;
-    if (pslot.empty()) plan->d_pslot = nullptr;
-    {
-        uint16_t *d_rank_ab = nullptr;
-        if ((rc = upload(arena, o_rankab, &d_rank_ab, rank_ab))) return rc;
-        plan->fold_reg.rank_ab = rank_ab.empty() ? nullptr : d_rank_ab;
-    }
-    plan->max_chunks_per_output = 0;
-    for (int o = 0; o < n_out; o++) plan->max_chunks_per_output = std::max<int>(plan->max_chunks_per_output, (int)(out_chunk_begin[o + 1] - out_chunk_begin[o]));
-    timer.lap("device arena + small uploads");
-    // scatter the values on the device: one launch per (output, group size) and layout
-    for (int o = 0; o < n_out; o++) {
+    if ((rc = upload(arena, o_perm, &lay.d_perm, lay.perm))) return rc;
+    if ((rc = upload(arena, o_pslot, &plan->d_pslot, lay.pslot))) return rc;
+    if (lay.pslot.empty()) plan->d_pslot = nullptr;
+    uint16_t *d_rank_ab = nullptr;
+    if ((rc = upload(arena, o_rankab, &d_rank_ab, lay.rank_ab))) return rc;
+    plan->fold_reg.rank_ab = lay.rank_ab.empty() ? nullptr : d_rank_ab;
+    return BLUEST_OK;
+}
+
+// scatter the values on the device (one launch per (output, group size) and layout); clear the partials and the ticket
+static int scatter_values(bluest_plan_t plan, const PlanLayout &lay)
+{
+    for (int o = 0; o < (int)plan->outs.size(); o++) {
         const OutputDesc &od = plan->outs[o];
         const int st = plan->shared ? 0 : o;
         int64_t io = 0, go = 0, eo = 0;
@@ -1263,25 +1241,60 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
             const int ne = k * (k + 1) / 2;
             if (Lk > 0) {
                 hipLaunchKernelGGL(k_fill_csr, dim3((unsigned)((Lk * ne + 255) / 256)), dim3(256), 0, 0, od.d_invcov + io, k, Lk,
-                                   d_perm + struct_entries[st] + eo, plan->d_vals + out_chunk_begin[o] * CH);
+                                   lay.d_perm + lay.struct_entries[st] + eo, plan->d_vals + lay.out_chunk_begin[o] * lay.CH);
                 hipLaunchKernelGGL(k_fill_tiles, dim3((unsigned)((Lk * (ne + k) + 255) / 256)), dim3(256), 0, 0, od.d_invcov + io,
-                                   od.d_groups + go, k, Lk, plan->d_tvals + bucket_val[o][k]);
+                                   od.d_groups + go, k, Lk, plan->d_tvals + lay.bucket_val[o][k]);
             }
             io += Lk * k * k; go += Lk * k; eo += Lk * ne;
         }
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(0));
-    plan->d_partial = reinterpret_cast<double2 *>(arena.base + o_partial);
     // regular rows read slots no chunk writes: they stay zero for the plan's life
     if (plan->fold_reg.Cd > 0) {
-        HIP_TRY(hipMemsetAsync(plan->d_partial, 0, (size_t)max_candidates * plan->partial_stride * sizeof(double2), 0));
+        HIP_TRY(hipMemsetAsync(plan->d_partial, 0, (size_t)plan->max_cand * plan->partial_stride * sizeof(double2), 0));
         HIP_TRY(hipStreamSynchronize(0));
     }
-    plan->d_v = reinterpret_cast<double *>(arena.base + o_v);
-    plan->d_status = reinterpret_cast<int32_t *>(arena.base + o_status);
-    plan->d_ticket = reinterpret_cast<unsigned int *>(arena.base + o_ticket);
     HIP_TRY(hipMemset(plan->d_ticket, 0, 256));
+    return BLUEST_OK;
+}
+
+extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
+{
+    if (!plan) return fail(BLUEST_ERR_ARG, "plan is NULL");
+    if (plan->finalized) return fail(BLUEST_ERR_STATE, "plan already finalized");
+    if (plan->outs.empty()) return fail(BLUEST_ERR_STATE, "plan has no outputs");
+    if (max_candidates <= 0 || max_candidates > 65535) return fail(BLUEST_ERR_ARG, "max_candidates=%d out of range", max_candidates);
+    const int N = plan->N, n_out = (int)plan->outs.size();
+    PhaseTimer timer("plan_finalize");
+
+    plan->nsym = N * (N + 1) / 2;
+    plan->max_cand = max_candidates;
+    plan->shared = true;
+    for (int o = 1; o < n_out; o++) {
+        const OutputDesc &x = plan->outs[0], &y = plan->outs[o];
+        if (x.K != y.K || x.sizes != y.sizes || x.groups != y.groups || x.mapping != y.mapping) { plan->shared = false; break; }
+    }
+    // distinct STRUCTURES: with identical group lists and mappings every output has the same rows, chunks and slots, so the
+    // counting sort runs once and the other outputs reuse its result shifted by their chunk base
+    PlanLayout lay(n_out, plan->nsym, plan->shared ? 1 : n_out);
+    int rc;
+    if ((rc = layout_tiles(plan, lay))) return rc;
+    plan->identity = plan->shared && plan->outs[0].L_o == plan->L;
+    for (int64_t li = 0; plan->identity && li < plan->L; li++) plan->identity = plan->outs[0].mapping[li] == li;
+    if ((rc = layout_phi(plan, lay, timer))) return rc;
+    layout_fold_reg(plan, lay);
+    timer.lap("CSR slots + columns");
+    layout_invmap(plan, lay);
+    plan->cols16 = plan->L <= 65536 && getenv("BLUEST_COLS32") == nullptr;       // (A/B switch: BLUEST_COLS32=1 keeps int32 columns)
+    plan->phi_bytes = plan->n_chunks * lay.CH * 8 + (plan->shared ? plan->n_chunks / n_out : plan->n_chunks) * lay.CH * (plan->cols16 ? 2 : 4) + plan->n_chunks * 16;
+    plan->grad_bytes = (int64_t)lay.n_tvals * 8 + plan->grad_len * 8;
+    const char *nt_env = getenv("BLUEST_TILE_NT");              // A/B switch, read per plan: 0 = plain loads
+    plan->tile_nt = nt_env ? atoi(nt_env) != 0 : true;
+    timer.lap("tile descriptors + inverse maps");
+    if ((rc = arena_upload(plan, lay))) return rc;
+    timer.lap("device arena + small uploads");
+    if ((rc = scatter_values(plan, lay))) return rc;
     plan->finalized = true;
     if ((rc = mf_finalize(plan))) return rc;      // matrix-free evaluation for plans that qualify (matfree.hip)
 
@@ -1427,15 +1440,36 @@ extern "C" int bluest_plan_phi_len(bluest_plan_t plan, int64_t *len)
 static void launch_grad(bluest_plan_t plan, const double *v_dev, const int32_t *status_dev, int n_cand, double *grad_dev,
                         int64_t grad_stride, hipStream_t st)
 {
+    dispatch_le<5, 8, 12>(plan->kmax, [&](auto ku) {
+        hipLaunchKernelGGL((k_grad_tiles<decltype(ku)::value>), dim3((unsigned)((plan->n_tiles + 3) / 4)), dim3(256), 0, st, plan->d_tiles,
+                           plan->n_tiles, plan->d_tvals, v_dev, status_dev, plan->N, (int)plan->outs.size(), n_cand, grad_dev, grad_stride, plan->gate);
+    });
+}
+
+// the solve from Phi records (n_cand candidates): var / v / status
+static void launch_solve_from_record(bluest_plan_t plan, const double *rec, int n_cand, double delta, int want_v, double *var_dev,
+                                     double *v_dev, int32_t *status_dev, hipStream_t st)
+{
     const int n_out = (int)plan->outs.size();
-    int kmax = 0;
-    for (const auto &od : plan->outs) kmax = std::max(kmax, od.K);
-#define LG(KU) hipLaunchKernelGGL((k_grad_tiles<KU>), dim3((unsigned)((plan->n_tiles + 3) / 4)), dim3(256), 0, st, plan->d_tiles, plan->n_tiles, \
-                                  plan->d_tvals, v_dev, status_dev, plan->N, n_out, n_cand, grad_dev, grad_stride, plan->gate)
-    if (kmax <= 5) LG(5);
-    else if (kmax <= 8) LG(8);
-    else LG(12);
-#undef LG
+    nt_dispatch(plan->N, [&](auto nt) {
+        hipLaunchKernelGGL((k_solve_from_record<decltype(nt)::value>), dim3(n_out, n_cand), dim3(64), 0, st, plan->N, n_out, rec, delta, want_v,
+                           var_dev, v_dev, status_dev);
+    });
+}
+
+// the fused solve + gradient pass of one candidate: from a Phi record (rec != NULL, sharded plans) or from the chunk partials the Phi
+// pass left; optionally the SPG line-search decision in the tail (dec_state) or the multiplicative update instead of the gradient (ma)
+static void launch_solve_grad(bluest_plan_t plan, const double *rec, double delta, double *var_dev, int32_t *status_dev, double *grad_dev,
+                              double *dec_state, int dec_last, int32_t *dec_enable, MaTail ma, hipStream_t st)
+{
+    const int n_out = (int)plan->outs.size();
+    const dim3 grid((unsigned)(plan->n_tiles / plan->fused_tpb));
+    nt_dispatch(plan->N, [&](auto nt) { solve_grad_ku_dispatch(plan->kmax, [&](auto ku) {
+        constexpr int NT = decltype(nt)::value, KU = decltype(ku)::value;
+        hipLaunchKernelGGL((k_solve_grad<NT, KU>), grid, dim3(64 * (fused_tpb(NT, KU) + 1)), 0, st, plan->N, n_out, plan->d_rows, plan->nsym,
+                           plan->fold_reg, plan->d_partial, rec, delta, plan->d_tiles, plan->n_tiles, plan->fused_bpo, plan->fused_tpb, plan->tile_nt,
+                           plan->d_tvals, var_dev, plan->d_v, status_dev, grad_dev, plan->gate, dec_state, dec_last, dec_enable, plan->d_ticket, ma);
+    }); });
 }
 
 static void launch_chunks(bluest_plan_t p, const double *m, int n_cand, int64_t m_stride, hipStream_t st)
@@ -1482,10 +1516,10 @@ extern "C" int bluest_plan_phi(bluest_plan_t plan, const double *m_dev, int n_ca
     const int n_out = (int)plan->outs.size();
     if (plan->matfree && n_cand == 1 && !plan->gate) return mf_phi_record(plan, m_dev, phi_dev, nullptr, st);
     launch_chunks(plan, m_dev, n_cand, m_stride, st);
-#define LFR(NT) hipLaunchKernelGGL((k_fold_to_record<NT>), dim3(n_out, n_cand), dim3(fold_threads(NT)), 0, st, plan->N, n_out, plan->d_rows, \
-                                   plan->nsym, plan->fold_reg, plan->d_partial, plan->partial_stride, phi_dev)
-    NT_DISPATCH(plan->N, LFR);
-#undef LFR
+    nt_dispatch(plan->N, [&](auto nt) {
+        hipLaunchKernelGGL((k_fold_to_record<decltype(nt)::value>), dim3(n_out, n_cand), dim3(fold_threads(nt)), 0, st, plan->N, n_out, plan->d_rows,
+                           plan->nsym, plan->fold_reg, plan->d_partial, plan->partial_stride, phi_dev);
+    });
     HIP_TRY(hipGetLastError());
     return BLUEST_OK;
 }
@@ -1495,11 +1529,7 @@ extern "C" int bluest_plan_solve(bluest_plan_t plan, const double *phi_dev, int 
 {
     int rc = plan_ready(plan, n_cand); if (rc) return rc;
     if (!phi_dev || !var_dev || !v_dev || !status_dev) return fail(BLUEST_ERR_ARG, "null pointer");
-    const int n_out = (int)plan->outs.size();
-#define LSR(NT) hipLaunchKernelGGL((k_solve_from_record<NT>), dim3(n_out, n_cand), dim3(64), 0, (hipStream_t)stream, plan->N, n_out, \
-                                   phi_dev, delta, 1, var_dev, v_dev, status_dev)
-    NT_DISPATCH(plan->N, LSR);
-#undef LSR
+    launch_solve_from_record(plan, phi_dev, n_cand, delta, 1, var_dev, v_dev, status_dev, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return BLUEST_OK;
 }
@@ -1522,7 +1552,6 @@ extern "C" int bluest_plan_grad(bluest_plan_t plan, const double *v_dev, const i
     int rc = plan_ready(plan, n_cand); if (rc) return rc;
     if (!v_dev || !status_dev || !grad_dev) return fail(BLUEST_ERR_ARG, "null pointer");
     if (n_cand > 1 && grad_stride < plan->grad_len) return fail(BLUEST_ERR_ARG, "grad_stride < grad_len");
-    const int n_out = (int)plan->outs.size();
     if (plan->mf_gradient && n_cand == 1 && !plan->gate) return mf_grad(plan, v_dev, status_dev, grad_dev, (hipStream_t)stream);
     launch_grad(plan, v_dev, status_dev, n_cand, grad_dev, grad_stride, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
@@ -1551,16 +1580,7 @@ extern "C" int bluest_plan_solve_grad(bluest_plan_t plan, const double *rec_dev,
     if (state_dev && n_out > SPG_MAX_OUT) return fail(BLUEST_ERR_ARG, "more than %d outputs", SPG_MAX_OUT);
     hipStream_t st = (hipStream_t)stream;
     if (plan->mf_gradient && !state_dev && !plan->gate) return mf_solve_grad(plan, rec_dev, delta, var_dev, status_dev, grad_dev, st);
-    int kmax = 0;
-    for (const auto &od : plan->outs) kmax = std::max(kmax, od.K);
-    const dim3 grid((unsigned)(plan->n_tiles / plan->fused_tpb));
-#define LSR2(NT, KU) hipLaunchKernelGGL((k_solve_grad<NT, KU>), grid, dim3(64 * (fused_tpb(NT, KU) + 1)), 0, st, plan->N, n_out, plan->d_rows, plan->nsym, plan->fold_reg, plan->d_partial, \
-                                        rec_dev, delta, plan->d_tiles, plan->n_tiles, plan->fused_bpo, plan->fused_tpb, plan->tile_nt ? 1 : 0, plan->d_tvals, var_dev, plan->d_v, status_dev,  \
-                                        grad_dev, plan->gate, state_dev, last_slot, enable_dev, plan->d_ticket, MaTail{nullptr, nullptr, nullptr, nullptr})
-#define LSR(NT) do { if (kmax <= 5) LSR2(NT, 5); else if (kmax <= 6) LSR2(NT, 6); else if (kmax <= 8) LSR2(NT, 8); else LSR2(NT, 12); } while (0)
-    NT_DISPATCH(plan->N, LSR);
-#undef LSR
-#undef LSR2
+    launch_solve_grad(plan, rec_dev, delta, var_dev, status_dev, grad_dev, state_dev, last_slot, enable_dev, MaTail{nullptr, nullptr, nullptr, nullptr}, st);
     HIP_TRY(hipGetLastError());
     return BLUEST_OK;
 }
@@ -1597,37 +1617,25 @@ static int plan_eval(bluest_plan_t plan, const double *m_dev, int n_cand, int64_
         const double *rec = nullptr;
         if ((rc = mf_phi_record(plan, m_dev, nullptr, &rec, st))) return rc;
         if (grad_dev) return mf_solve_grad(plan, rec, delta, var_dev, status, grad_dev, st, ma);
-#define LSRM(NT) hipLaunchKernelGGL((k_solve_from_record<NT>), dim3(n_out, 1), dim3(64), 0, st, plan->N, n_out, rec, delta, plan->always_v ? 1 : 0, \
-                                    var_dev, plan->d_v, status)
-        NT_DISPATCH(plan->N, LSRM);
-#undef LSRM
+        launch_solve_from_record(plan, rec, 1, delta, plan->always_v ? 1 : 0, var_dev, plan->d_v, status, st);
         HIP_TRY(hipGetLastError());
         return BLUEST_OK;
     }
     launch_chunks(plan, m_dev, n_cand, m_stride, st);
     if (plan->mf_gradient && grad_dev && n_cand == 1 && !dec_state && !plan->gate)
         return mf_solve_grad(plan, nullptr, delta, var_dev, status, grad_dev, st, ma);  // stored Phi pass + fold, solve and matrix-free gradient
-    int kmax = 0;
-    for (const auto &od : plan->outs) kmax = std::max(kmax, od.K);
     // fused solve + gradient pass (2 launches per evaluation); groups larger than 12 take the generic tile code inside it
     if (grad_dev && n_cand == 1) {
-        const dim3 grid((unsigned)(plan->n_tiles / plan->fused_tpb));
-#define LSG2(NT, KU) hipLaunchKernelGGL((k_solve_grad<NT, KU>), grid, dim3(64 * (fused_tpb(NT, KU) + 1)), 0, st, plan->N, n_out, plan->d_rows, plan->nsym, plan->fold_reg, plan->d_partial, nullptr, \
-                                        delta, plan->d_tiles, plan->n_tiles, plan->fused_bpo, plan->fused_tpb, plan->tile_nt ? 1 : 0, plan->d_tvals, var_dev, plan->d_v, status, grad_dev, plan->gate, \
-                                        dec_state, dec_last, dec_enable, plan->d_ticket, ma)
-#define LSG(NT) do { if (kmax <= 5) LSG2(NT, 5); else if (kmax <= 6) LSG2(NT, 6); else if (kmax <= 8) LSG2(NT, 8); else LSG2(NT, 12); } while (0)
-        NT_DISPATCH(plan->N, LSG);
-#undef LSG
-#undef LSG2
+        launch_solve_grad(plan, nullptr, delta, var_dev, status, grad_dev, dec_state, dec_last, dec_enable, ma, st);
         HIP_TRY(hipGetLastError());
         return BLUEST_OK;
     }
     const int want = (grad_dev || plan->always_v) ? 1 : 0;
-#define LSC(NT) hipLaunchKernelGGL((k_solve_from_chunks<NT>), dim3(n_out, n_cand), dim3(fold_threads(NT)), 0, st, plan->N, n_out, plan->d_rows, \
-                                   plan->nsym, plan->fold_reg, plan->d_partial, plan->partial_stride, delta, want, var_dev, plan->d_v, status, plan->gate, \
-                                   dec_state, dec_last, dec_enable, plan->d_ticket)
-    NT_DISPATCH(plan->N, LSC);
-#undef LSC
+    nt_dispatch(plan->N, [&](auto nt) {
+        hipLaunchKernelGGL((k_solve_from_chunks<decltype(nt)::value>), dim3(n_out, n_cand), dim3(fold_threads(nt)), 0, st, plan->N, n_out, plan->d_rows,
+                           plan->nsym, plan->fold_reg, plan->d_partial, plan->partial_stride, delta, want, var_dev, plan->d_v, status, plan->gate,
+                           dec_state, dec_last, dec_enable, plan->d_ticket);
+    });
     if (grad_dev)
         launch_grad(plan, plan->d_v, status, n_cand, grad_dev, grad_stride, st);
     HIP_TRY(hipGetLastError());
@@ -1649,9 +1657,7 @@ extern "C" int bluest_plan_eval_ma(bluest_plan_t plan, double *m_dev, double *va
 {
     if (!plan || !m_dev || !var_dev || !status_dev || !s_dev || !cc_dev || !x_dev) return fail(BLUEST_ERR_ARG, "null pointer");
     if (!plan->finalized) return fail(BLUEST_ERR_STATE, "plan not finalized");
-    int kmax = 0;
-    for (const auto &od : plan->outs) kmax = std::max(kmax, od.K);
-    if (plan->outs.size() != 1 || !plan->identity || plan->gate || kmax > (plan->matfree ? 8 : 12))
+    if (plan->outs.size() != 1 || !plan->identity || plan->gate || plan->kmax > (plan->matfree ? 8 : 12))
         return fail(BLUEST_ERR_STATE, "bluest_plan_eval_ma: one output on all groups under the identity mapping only");
     // (the gradient pointer only selects the fused kernel: with the tail on, nothing is written through it)
     return plan_eval(plan, m_dev, 1, 0, 0.0, var_dev, plan->d_v, plan->grad_len, status_dev, stream, nullptr, 0, nullptr, MaTail{x_dev, cc_dev, m_dev, s_dev});

@@ -45,6 +45,9 @@ struct bluest_plan_s {
     int iters = 1;  // chunk = 256*iters entries
     bool shared = false;  // all outputs have identical groups + mapping
     bool identity = false; // ... and that mapping is the identity (local index = global index for every output)
+    int kmax = 0;         // largest group size over the outputs (picks the KU instantiation of the tile kernels)
+    bool spg_small = false;   // small plan: the gradient tiles of the accepted SPG point run inside the single-workgroup finishing
+                              // kernel (bluest_spg_finish, bluest_spg_window); else every evaluation is the fused solve + gradient launch
     int fused_bpo = 0;    // workgroups of k_solve_grad per output when that is the same for every output, else 0
     int fused_tpb = 15;   // tiles per workgroup of k_solve_grad for this plan (tile list is padded to it per output)
     bool tile_nt = true;  // k_solve_grad streams its tiles with non-temporal loads (same-box A/B over six shapes: 12.8 vs 14.3 us
@@ -52,7 +55,7 @@ struct bluest_plan_s {
     const int32_t *gate = nullptr;  // optional device word: 0 = skip the plan's kernels (bluest_plan_set_gate)
     bool always_v = false;          // compute v in every solve (device-side SPG keeps the accepted trial's v)
     int nsym = 0;
-    int64_t n_chunks = 0, n_rows = 0, n_tiles = 0, grad_len = 0;
+    int64_t n_chunks = 0, n_tiles = 0, grad_len = 0;
     std::vector<int64_t> grad_off;
     int64_t phi_bytes = 0, grad_bytes = 0;
     // device
@@ -60,9 +63,6 @@ struct bluest_plan_s {
     int32_t *d_cols = nullptr;          // columns of the Phi layout; holds uint16 entries when cols16 (allocation vectors of <= 65 536 entries)
     bool cols16 = false;
     RowDesc *d_rows = nullptr;
-    int32_t *d_out_row_begin = nullptr;
-    int64_t *d_out_chunk_begin = nullptr;   // n_out + 1: first chunk of every output (its partials are contiguous)
-    int max_chunks_per_output = 0;
     TileDesc *d_tiles = nullptr;
     double *d_tvals = nullptr;   // tiles: slot pairs (see TileDesc)
     int32_t *d_invmap = nullptr;
@@ -83,23 +83,21 @@ struct bluest_plan_s {
     // matrix-free evaluation (matfree.hip): chosen at finalize for plans that qualify
     bool matfree = false;        // Phi pass and gradient pass matrix-free
     bool mf_gradient = false;    // gradient pass matrix-free (also true when matfree): the stored Phi pass + k_solve_grad_mf folding its partials
-    void *mf = nullptr;
-    int32_t *mf_wg_begin_dev = nullptr;
-    int mf_wgs_grad = 0, mf_bpo = 0;
+    void *mf = nullptr;          // MfState (matfree.hip)
     void *d_master = nullptr;
     size_t master_bytes = 0;
     std::vector<std::vector<int32_t>> inv_host;
 };
 
 // current device for the lifetime of the object (a plan's memory and kernels live on plan->device)
-struct DeviceScopeN {
+struct DeviceScope {
     int prev = -1;
     bool switched = false;
-    explicit DeviceScopeN(int dev)
+    explicit DeviceScope(int dev)
     {
         if (hipGetDevice(&prev) == hipSuccess && prev != dev && dev >= 0) switched = hipSetDevice(dev) == hipSuccess;
     }
-    ~DeviceScopeN() { if (switched) (void)hipSetDevice(prev); }
+    ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
 };
 
 

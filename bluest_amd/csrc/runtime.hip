@@ -1,5 +1,6 @@
 // runtime.hip -- error state, ABI version, device queries of libbluest_hip.so (include/bluest_hip.h, top).
 #include "common.hpp"
+#include <map>
 
 static thread_local std::string g_last_error;
 
@@ -24,6 +25,22 @@ int require_gpu()
                     e == hipSuccess ? "0 devices" : hipGetErrorString(e));
     }
     return BLUEST_OK;
+}
+
+hipError_t device_props(int dev, DeviceProps *out)
+{
+    static std::mutex mutex;
+    static std::map<int, DeviceProps> cache;      // hipGetDeviceProperties costs a millisecond or more
+    std::lock_guard<std::mutex> lock(mutex);
+    auto it = cache.find(dev);
+    if (it == cache.end()) {
+        hipDeviceProp_t p;
+        const hipError_t e = hipGetDeviceProperties(&p, dev);
+        if (e != hipSuccess) return e;
+        it = cache.emplace(dev, DeviceProps{p.multiProcessorCount, p.sharedMemPerBlock}).first;
+    }
+    *out = it->second;
+    return hipSuccess;
 }
 
 extern "C" int bluest_abi_version(void) { return BLUEST_ABI_VERSION; }

@@ -466,17 +466,15 @@ __device__ __forceinline__ void solve_wave(SolveLds<NT> &lds, int N, double delt
 // matrix of the solving wavefront fits the 128-VGPR budget that comes with it, else 256
 __host__ __device__ constexpr int fold_threads(int NT) { return NT <= 26 ? 1024 : 256; }
 
-// host-side choice of the register-array size NT >= N
-#define NT_DISPATCH(N, LAUNCH)                                                                                \
-    do {                                                                                                     \
-        if (N <= 8) { LAUNCH(8); }                                                                           \
-        else if (N <= 12) { LAUNCH(12); }                                                                    \
-        else if (N <= 16) { LAUNCH(16); }                                                                    \
-        else if (N <= 20) { LAUNCH(20); }                                                                    \
-        else if (N <= 26) { LAUNCH(26); }                                                                    \
-        else if (N <= 32) { LAUNCH(32); }                                                                    \
-        else if (N <= 48) { LAUNCH(48); }                                                                    \
-        else { LAUNCH(64); }                                                                                 \
-    } while (0)
+// host-side choice of a kernel's instantiation: the first of VS... that covers x (x <= V), else the last one; launch receives
+// it as std::integral_constant<int, V>
+template <int V, int... VS, class F>
+inline void dispatch_le(int x, F &&launch)
+{
+    if constexpr (sizeof...(VS) > 0) { if (x > V) return dispatch_le<VS...>(x, launch); }
+    launch(std::integral_constant<int, V>{});
+}
+// the register-array size NT >= N
+template <class F> inline void nt_dispatch(int N, F &&launch) { dispatch_le<8, 12, 16, 20, 26, 32, 48, 64>(N, launch); }
 
-static inline int pick_nt(int N) { return N <= 8 ? 8 : N <= 12 ? 12 : N <= 16 ? 16 : N <= 20 ? 20 : N <= 26 ? 26 : N <= 32 ? 32 : N <= 48 ? 48 : 64; }
+static inline int pick_nt(int N) { int nt = 0; nt_dispatch(N, [&](auto v) { nt = v; }); return nt; }

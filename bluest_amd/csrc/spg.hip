@@ -1027,21 +1027,15 @@ static int simplex_impl(const double *x_dev, const double *g_dev, double lambda,
     if (ws && L > 4096) {   // long vector: streaming parts on many CUs
         const int nb = (int)((L + 1023) / 1024);
         {   // single launch with grid barriers while (r, s) of the whole vector fit the registers of <= #CU workgroups
-            static int ncu_of[64] = {0};          // compute units per device (index = HIP device id)
             int dev = 0;
             HIP_TRY(hipGetDevice(&dev));
-            if (dev < 0 || dev >= 64) return fail(BLUEST_ERR_ARG, "device id %d out of range", dev);
-            if (!ncu_of[dev]) {
-                hipDeviceProp_t prop;
-                HIP_TRY(hipGetDeviceProperties(&prop, dev));
-                ncu_of[dev] = prop.multiProcessorCount;
-            }
-            const int ncu = ncu_of[dev];
+            DeviceProps dp;
+            HIP_TRY(device_props(dev, &dp));
             // workgroup size: 256 threads when 64 of them hold the vector with <= 4 entries per thread (K_tot <= 65536), else 1024
             const int bt = L <= 64LL * 256 * 4 ? 256 : 1024;
             const int nb_bt = (int)((L + bt - 1) / bt);
             // at most 64 workgroups (one wavefront folds the messages; 64 measured best at L = 245505: 61 -> 42 us)
-            const int nbf = std::max(1, std::min(std::min(nb_bt, ncu), 64));
+            const int nbf = std::max(1, std::min(std::min(nb_bt, dp.cus), 64));
             const int64_t items = (L + (int64_t)bt * nbf - 1) / ((int64_t)bt * nbf);
             if (items <= 16 && !getenv("BLUEST_PROJ_MULTI_LAUNCH")) {
 #define PF(IT) hipLaunchKernelGGL((k_proj_fused<IT>), dim3(nbf), dim3(bt), 0, st, x_dev, g_dev, lambda, z, floor, L, ws, nb, p_dev, d_dev, \
@@ -1179,17 +1173,13 @@ extern "C" int bluest_spg_finish(bluest_plan_t plan, const double *v_dev, const 
     int rc = plan_ready(plan, 1); if (rc) return rc;
     if (!v_dev || !status_dev || !x_dev || !g_dev || !xnew_dev || !grad_dev || !scale_dev || !state_dev || !work_dev)
         return fail(BLUEST_ERR_ARG, "null pointer");
-    if (plan->L <= 4096 && plan->n_tiles <= 1024) {
-        int kmax = 0;
-        for (const auto &od : plan->outs) kmax = std::max(kmax, od.K);
+    if (plan->spg_small) {
         // 1024 threads: the tile rounds dominate (measured 13.0 / 14.1 / 18.0 us with 1024 / 512 / 256 threads)
-#define LFS(KU) hipLaunchKernelGGL((k_spg_finish_small<KU>), dim3(1), dim3(1024), 0, (hipStream_t)stream, plan->d_tiles, plan->n_tiles, \
-                                   plan->d_tvals, v_dev, status_dev, plan->N, (int)plan->outs.size(), grad_dev, x_dev, g_dev,    \
-                                   xnew_dev, plan->d_goff, plan->d_invmap, scale_dev, state_dev, floor, plan->L)
-        if (kmax <= 5) LFS(5);
-        else if (kmax <= 8) LFS(8);
-        else LFS(12);
-#undef LFS
+        dispatch_le<5, 8, 12>(plan->kmax, [&](auto ku) {
+            hipLaunchKernelGGL((k_spg_finish_small<decltype(ku)::value>), dim3(1), dim3(1024), 0, (hipStream_t)stream, plan->d_tiles,
+                               plan->n_tiles, plan->d_tvals, v_dev, status_dev, plan->N, (int)plan->outs.size(), grad_dev, x_dev, g_dev,
+                               xnew_dev, plan->d_goff, plan->d_invmap, scale_dev, state_dev, floor, plan->L);
+        });
         HIP_TRY(hipGetLastError());
         return BLUEST_OK;
     }
@@ -1228,9 +1218,7 @@ extern "C" int bluest_spg_window(bluest_plan_t plan, double *x_dev, double *g_de
         return fail(BLUEST_ERR_ARG, "null pointer");
     if (slots < 1 || slots > 8 || n_iterations < 0) return fail(BLUEST_ERR_ARG, "slots=%d, n_iterations=%d out of range", slots, n_iterations);
     const int64_t L = plan->L;
-    // small plans: the gradient tiles of the accepted point run inside the single-workgroup finishing kernel; large plans: every
-    // evaluation is the fused solve + gradient launch (decision in its tail), so the update follows the line search directly
-    const bool small = plan->L <= 4096 && plan->n_tiles <= 1024;
+    const bool small = plan->spg_small;       // else the decision sits in the fused launch's tail and the update follows the line search
     for (int it = 0; it < n_iterations; it++) {
         if ((rc = bluest_spg_direction(x_dev, g_dev, state_dev, 1.0, floor, L, d_dev, scale_dev, xnew_dev, m_dev, enable_dev, proj_work_dev, stream))) return rc;
         for (int t = 0; t < slots; t++) {
