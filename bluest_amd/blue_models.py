@@ -24,7 +24,6 @@ and the problem is verbose, project_covariance() prints a warning and returns th
 unless bypass_error_check=True; a problem that is not verbose is always updated.
 """
 import ctypes
-from itertools import combinations
 
 import numpy as np
 
@@ -131,19 +130,26 @@ class _Coupling(object):
         return bool(self.linked[np.ix_(g, g)].all()) and all(int(i) in set(self.component) for i in g)
 
     def cliques(self, K):
-        """all cliques of up to K models inside model 0's component, per size, each sorted, lexicographic order"""
-        nodes = self.component
+        """all cliques of up to K models inside model 0's component, per size, each sorted, lexicographic order.  One size at a
+        time over all its cliques: a (k-1)-clique c extends by every model j > c[-1] linked to all of c; the candidates are a
+        64-bit mask per clique (the AND of the members' masks of linked larger models), and numpy.nonzero over the
+        (clique, j) bit matrix lists the extensions row-major -- parent first, j ascending -- which keeps the order lexicographic"""
+        nodes = np.asarray(self.component, dtype=np.int64)
+        n = len(nodes)
         sub = self.linked[np.ix_(nodes, nodes)]
-        if sub.all():
-            return [np.array(list(combinations(nodes, k)), dtype=np.int64).reshape(-1, k) for k in range(1, K + 1)]
-        out = [[(i,) for i in nodes]]
-        for k in range(2, K + 1):                                # extend every (k-1)-clique by a larger, fully linked model
-            bigger = []
-            for c in out[-1]:
-                cand = self.linked[list(c)].all(axis=0)
-                bigger += [c + (j,) for j in nodes if j > c[-1] and cand[j]]
-            out.append(bigger)
-        return [np.array(level, dtype=np.int64).reshape(-1, k + 1) for k, level in enumerate(out)]
+        bit = np.left_shift(np.uint64(1), np.arange(n, dtype=np.uint64))
+        higher = np.array([np.bitwise_or.reduce(bit[(np.arange(n) > i) & sub[i]], initial=np.uint64(0)) for i in range(n)],
+                          dtype=np.uint64)
+        rows = np.arange(n, dtype=np.int64).reshape(-1, 1)         # local indices (nodes is ascending: same order as the models)
+        cand = higher.copy()
+        out = [rows]
+        for k in range(2, K + 1):
+            ext = ((cand[:, None] & bit[None, :]) != 0)
+            parent, j = np.nonzero(ext)
+            rows = np.concatenate([rows[parent], j[:, None].astype(np.int64)], axis=1)
+            cand = cand[parent] & higher[j]
+            out.append(rows)
+        return [nodes[r].reshape(-1, k + 1) for k, r in enumerate(out)]
 
 
 class BLUEProblem(object):

@@ -72,6 +72,14 @@ def top_candidates(topv, topi, k):
     return topi[head][o].tolist(), topv[head][o].tolist()
 
 
+def _fused_ma_ok(plan):
+    """the plan's widest group is within what bluest_plan_eval_ma accepts on it (both read from the plan)"""
+    lim, km = ctypes.c_int(0), ctypes.c_int(0)
+    check(plan.lib.bluest_plan_eval_ma_kmax(plan._h, ctypes.byref(lim)))
+    check(plan.lib.bluest_plan_kmax(plan._h, ctypes.byref(km)))
+    return 0 < km.value <= lim.value
+
+
 def master_max_support(plan):
     s = ctypes.c_int(0)
     with torch.cuda.device(plan.device):
@@ -216,7 +224,8 @@ def colgen_solve(plan, costs, s, B, x0=None, prm=None, log=None, caps=None):
         _t_ma0 = _time.perf_counter()
         # a single output on all groups: the fused solve + gradient kernel of the evaluation applies the update itself (two launches
         # per step instead of three, no gradient array; the same iterates bit for bit)
-        fused_ma = sharded is None and n_out == 1 and bool(getattr(plan, "identity", False))
+        # (only while the plan's widest group is within what that kernel's tail handles: the plan reports both)
+        fused_ma = sharded is None and n_out == 1 and bool(getattr(plan, "identity", False)) and _fused_ma_ok(plan)
         for _ in range(ma_its):
             if fused_ma:
                 check(lib.bluest_plan_eval_ma(plan._h, m_d.data_ptr(), var.data_ptr(), status.data_ptr(), s_d.data_ptr(), cc.data_ptr(), x_d.data_ptr(), st))

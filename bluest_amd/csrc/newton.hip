@@ -27,10 +27,13 @@
                                // after a rejection 0-3 % faster on the synthetic shapes, but the ill-conditioned Navier-Stokes problem's
                                // certified gap went to 6e-5 under perturbed parameters)
 #define MASTER_DAMP_UP 10.0    // ... after a rejected step
+#define MASTER_KB_MAX 16          // bluest_master_max_support: groups wider than this are counted as the support's few wide entries ...
+#define MASTER_WIDE_IN_SUPPORT 2  // ... of which it assumes this many
 #define MASTER_STATIC_LDS 2048   // room kept for the kernel's static LDS (the small KKT system: 1.5 KB) next to the dynamic part
 
 struct MasterArgs {
     int N, n_out, S, KM;               // models, outputs, support size (<= 64), largest group size in the support
+    int sumKE, sumK;                   // sum over the support of k_j (k_j + 1) / 2 (packed block entries) and of k_j
     double eps_bg, tol, act_tol, floor_x;
     double fb;                         // > 0: fraction-to-the-boundary rule (no entry reaches zero: the polish without background)
     int maxit;
@@ -57,39 +60,42 @@ struct MasterArgs {
 __host__ __device__ constexpr int master_phi_doubles(int N, int nt) { return nt ? nt * (nt + 2) : N * (N + 1); }
 
 struct MasterLds {                     // carved out of dynamic LDS by master_carve()
-    double *PHI, *TACT, *BLK, *M, *AAC, *GQ;
+    double *PHI, *TACT, *BLK, *M, *AAC, *GQ;   // BLK / AAC: every support block at its own size (offsets in bo)
     double *x, *xt, *xp, *d, *cc, *Dm, *glv, *mvec, *hd, *r, *rt, *rp, *mu, *mup, *muh, *scal, *capb, *capslack, *nu;      // hd: undamped diagonal of the iteration's Hessian (free-set order)
     double *fcol;                      // [2][72]: multiplier column + pivot of the factorisation's current step (double-buffered)
     int *kk, *fi, *act, *istate, *capmodel, *actc;
     signed char *pos;
     unsigned char *idx;
     unsigned long long *memb;          // [N] bit j: support group j contains the model
-    unsigned short *dl_off, *dl_ab, *dl_ent;   // destination lists of the Phi assembly: offsets [ND + 1], (a | b << 8) [ND], entries j | e << 7
-    int LDN, LDM, KE, ND, PHS;         // PHS: doubles per output in PHI
+    unsigned *bo;                      // [S] exclusive prefix sums over the support: packed entries (bits 0-15) | model slots (bits 16-31)
+    unsigned short *dl_off, *dl_ab, *dl_ent;   // destination lists of the Phi assembly: offsets [ND + 1], (a | b << 8) [ND], entries j | e << 6
+    int LDN, LDM, ND, PHS, SK;         // PHS: doubles per output in PHI; SK = sum_j k_j (AAC stride per active output)
 };
 
-__host__ __device__ inline size_t master_lds_bytes(int N, int n_out, int S, int KM, int nt)
+// sumKE / sumK: the support's packed block entries / model slots (S KE(KM) and S KM when every group has KM models).  Each support
+// block is stored at its own size, so one or two wide groups cost their own entries, not KE(KM) for every support entry.
+__host__ __device__ inline size_t master_lds_bytes(int N, int n_out, int S, int KM, int nt, int sumKE, int sumK)
 {
-    const size_t LDN = N + 1, LDM = (S + MASTER_NE + 1) | 1, KE = (size_t)KM * (KM + 1) / 2, ND = (size_t)N * (N + 1) / 2;
+    const size_t LDN = N + 1, LDM = (S + MASTER_NE + 1) | 1, ND = (size_t)N * (N + 1) / 2;
     const size_t PA = n_out < MASTER_PACT ? n_out : MASTER_PACT;      // active outputs there can be: T and the a_{o,j} are kept for those only
-    size_t d = (size_t)n_out * master_phi_doubles(N, nt) + PA * N * LDN + (size_t)S * n_out * KE + (size_t)S * LDM +
-               PA * S * KM + (size_t)S * MASTER_PACT + 9 * (size_t)S + 6 * (size_t)n_out + 256 + 3 * 64 + (size_t)N + 2 * 72;
+    size_t d = (size_t)n_out * master_phi_doubles(N, nt) + PA * N * LDN + (size_t)n_out * sumKE + (size_t)S * LDM +
+               PA * sumK + (size_t)S * MASTER_PACT + 9 * (size_t)S + 6 * (size_t)n_out + 256 + 3 * 64 + (size_t)N + 2 * 72;
     size_t bytes = d * sizeof(double) + (3 * (size_t)S + 2 * MASTER_PACT + 48 + 64 + 2 * MASTER_MCAP) * sizeof(int) + (size_t)S * N + (size_t)S * KM + 64;
     bytes = (bytes + 7) & ~(size_t)7;
-    bytes += (2 * ND + 2 + (size_t)S * KE + 8) * sizeof(unsigned short);
+    bytes += (2 * ND + 2 + (size_t)sumKE + 8) * sizeof(unsigned short);
     return (bytes + 15) & ~(size_t)15;
 }
 
-__device__ inline void master_carve(MasterLds &L, unsigned char *base, int N, int n_out, int S, int KM, int nt)
+__device__ inline void master_carve(MasterLds &L, unsigned char *base, int N, int n_out, int S, int KM, int nt, int sumKE, int sumK)
 {
-    L.LDN = N + 1; L.LDM = (S + MASTER_NE + 1) | 1; L.KE = KM * (KM + 1) / 2; L.ND = N * (N + 1) / 2; L.PHS = master_phi_doubles(N, nt);
+    L.LDN = N + 1; L.LDM = (S + MASTER_NE + 1) | 1; L.ND = N * (N + 1) / 2; L.PHS = master_phi_doubles(N, nt); L.SK = sumK;
     double *p = reinterpret_cast<double *>(base);
     L.PHI = p;  p += (size_t)n_out * L.PHS;
     const size_t PA = n_out < MASTER_PACT ? n_out : MASTER_PACT;
     L.TACT = p; p += PA * N * L.LDN;
-    L.BLK = p;  p += (size_t)S * n_out * L.KE;
+    L.BLK = p;  p += (size_t)n_out * sumKE;
     L.M = p;    p += (size_t)S * L.LDM;
-    L.AAC = p;  p += PA * S * KM;
+    L.AAC = p;  p += PA * sumK;
     L.GQ = p;   p += (size_t)S * MASTER_PACT;
     L.x = p; p += S; L.xt = p; p += S; L.xp = p; p += S; L.d = p; p += S; L.cc = p; p += S; L.Dm = p; p += S; L.glv = p; p += S; L.mvec = p; p += S; L.hd = p; p += S;
     L.r = p; p += n_out; L.rt = p; p += n_out; L.rp = p; p += n_out; L.mu = p; p += n_out; L.mup = p; p += n_out; L.muh = p; p += n_out;
@@ -100,7 +106,7 @@ __device__ inline void master_carve(MasterLds &L, unsigned char *base, int N, in
     int *q = reinterpret_cast<int *>(p);
     L.kk = q; q += S; L.fi = q; q += S; L.act = q; q += 2 * MASTER_PACT; L.istate = q; q += 48;      // act: current list, then the iteration's list (act0)
     L.capmodel = q; q += 64; L.actc = q; q += 2 * MASTER_MCAP;                                       // actc: current caps of the step, then the iteration's (actc0)
-    q += S;     // spare
+    L.bo = reinterpret_cast<unsigned *>(q); q += S;
     L.pos = reinterpret_cast<signed char *>(q);
     L.idx = reinterpret_cast<unsigned char *>(L.pos + (size_t)S * N);
     size_t used = (size_t)((L.idx + (size_t)S * KM) - base);
@@ -109,6 +115,14 @@ __device__ inline void master_carve(MasterLds &L, unsigned char *base, int N, in
     L.dl_ab = L.dl_off + L.ND + 1;
     L.dl_ent = L.dl_ab + L.ND + 1;
 }
+
+// block of support group j for output o (packed symmetric, k_j (k_j + 1) / 2 entries); a_{o,j} of active output a (k_j entries)
+__device__ __forceinline__ const double *master_blk(const MasterLds &L, int n_out, int j, int o)
+{
+    const int k = L.kk[j];
+    return L.BLK + (size_t)(L.bo[j] & 0xffffu) * n_out + (size_t)o * (k * (k + 1) / 2);
+}
+__device__ __forceinline__ double *master_aac(const MasterLds &L, int a, int j) { return L.AAC + (size_t)a * L.SK + (L.bo[j] >> 16); }
 
 // scal[] slots
 enum { SC_F = 0, SC_LAMEST, SC_DAMP, SC_TAU, SC_LAM, SC_PRED, SC_KKT, SC_SPREAD, SC_QMAX, SC_FT, SC_LAMX, SC_MBEST, SC_FBEST, SC_KKTBEST, SC_SPREADBEST };
@@ -353,7 +367,7 @@ __device__ __forceinline__ double inv00_regs(const double *P, int N, int lane)
 template <int NT>
 __device__ void master_eval(const MasterArgs &A, MasterLds &L, const double *xv, double *rout, int tid)
 {
-    const int N = A.N, n_out = A.n_out, S = A.S, LDN = L.LDN, KE = L.KE, ND = L.ND, PHS = L.PHS;
+    const int N = A.N, n_out = A.n_out, S = A.S, LDN = L.LDN, ND = L.ND, PHS = L.PHS;
     const int wave = tid >> 6, lane = tid & 63, nw = MASTER_THREADS / 64;
     // the background's share first: all its loads are in flight together (one memory round trip per evaluation; loaded where
     // the sums are stored, every pass of the loop below waited for its own)
@@ -390,9 +404,10 @@ __device__ void master_eval(const MasterArgs &A, MasterLds &L, const double *xv,
             for (int q = 0; q < 8; q++) acc[q] = 0.0;
             for (int i = beg + sub; i < end; i += 4) {
                 const unsigned ent = L.dl_ent[i];
-                const int j = (int)(ent & 127u), e = (int)(ent >> 7);
+                const int j = (int)(ent & 63u), e = (int)(ent >> 6);
                 const double mj = L.mvec[j];
-                const double *B = L.BLK + (size_t)j * n_out * KE + e;
+                const int kj = L.kk[j], KE = kj * (kj + 1) / 2;
+                const double *B = L.BLK + (size_t)(L.bo[j] & 0xffffu) * n_out + e;
 #pragma unroll
                 for (int q = 0; q < 8; q++) if (o0 + q < n_out) acc[q] = fma(mj, B[(size_t)(o0 + q) * KE], acc[q]);
             }
@@ -453,7 +468,7 @@ __device__ void master_build_system(const MasterArgs &A, MasterLds &L, int tid, 
             const int o = L.act[a + MASTER_PACT];      // act0 list lives behind the current list
             const double ro = L.r[o];
             const double *T = L.TACT + (size_t)a * N * LDN;
-            const double *ai = L.AAC + ((size_t)a * S + i) * KM, *aj = L.AAC + ((size_t)a * S + j) * KM;
+            const double *ai = master_aac(L, a, i), *aj = master_aac(L, a, j);
             double acc = 0.0;
             for (int l = 0; l < ki; l++) {
                 const double *Trow = T + (size_t)L.idx[i * KM + l] * LDN;
@@ -791,9 +806,9 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
     extern __shared__ __align__(16) unsigned char master_sm[];
     MasterLds L;
     const int N = A.N, n_out = A.n_out, S = A.S, KM = A.KM;
-    master_carve(L, master_sm, N, n_out, S, KM, NT);
+    master_carve(L, master_sm, N, n_out, S, KM, NT, A.sumKE, A.sumK);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int LDN = L.LDN, KE = L.KE;
+    const int LDN = L.LDN, KE = KM * (KM + 1) / 2;
     // ---- load the support ---------------------------------------------------------------------------
     for (int j = tid; j < S; j += MASTER_THREADS) { L.kk[j] = A.kk[j]; L.cc[j] = A.cc[j]; const double v = A.x[j]; L.x[j] = v > 0.0 ? v : 0.0; }
     for (int t = tid; t < S * KM; t += MASTER_THREADS) L.idx[t] = A.idx[t];
@@ -803,6 +818,16 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
     for (int t = tid; t < 256; t += MASTER_THREADS) L.scal[t] = 0.0;
     for (int t = tid; t < n_out * L.PHS; t += MASTER_THREADS) L.PHI[t] = 0.0;      // pads of the reversed layout stay zero
     if (tid < 64) { L.capmodel[tid] = tid < A.ncap ? A.cap_model[tid] : 0; L.capb[tid] = tid < A.ncap ? A.cap_b[tid] : 0.0; L.nu[tid] = 0.0; L.capslack[tid] = 0.0; }
+    if (wave == 0) {   // offsets of the support blocks: exclusive scan of k (k + 1) / 2 and of k over the support (S <= 64: one pass)
+        const int k = lane < S ? A.kk[lane] : 0;
+        int ke = k * (k + 1) / 2, kq = k;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int e2 = __shfl_up(ke, off, WAVE), k2 = __shfl_up(kq, off, WAVE);
+            if (lane >= off) { ke += e2; kq += k2; }
+        }
+        if (lane < S) L.bo[lane] = (unsigned)(ke - k * (k + 1) / 2) | ((unsigned)(kq - k) << 16);
+    }
     __syncthreads();
     for (int t = tid; t < S * KM; t += MASTER_THREADS) {
         const int j = t / KM, l = t % KM;
@@ -811,16 +836,17 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
     for (int t = tid; t < S * n_out * KE; t += MASTER_THREADS) {
         const int e = t % KE, o = (t / KE) % n_out, j = t / (KE * n_out);
         const int k = L.kk[j];
+        if (e >= k * (k + 1) / 2) continue;
         double v = 0.0;
         const int64_t off = A.boff[(size_t)o * S + j];
-        if (off >= 0 && e < k * (k + 1) / 2) {
+        if (off >= 0) {
             int l = 0, rem = e;
             while (rem >= k - l) { rem -= k - l; l++; }
             const int l2 = l + rem;
             const double *b = A.invcov[o] + off;
             v = 0.5 * (b[l * k + l2] + b[l2 * k + l]);
         }
-        L.BLK[t] = v;
+        const_cast<double *>(master_blk(L, n_out, j, o))[e] = v;
     }
     // membership masks from the positions: lane = support group, one ballot per model
     __syncthreads();
@@ -863,7 +889,7 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
             both &= both - 1ull;
             const int pa = L.pos[j * N + a], pb = L.pos[j * N + b];
             const int lo = pa < pb ? pa : pb, hi = pa < pb ? pb : pa;
-            L.dl_ent[o++] = (unsigned short)(j | (sym_e(lo, hi, L.kk[j]) << 7));
+            L.dl_ent[o++] = (unsigned short)(j | (sym_e(lo, hi, L.kk[j]) << 6));      // j < 64, e < KE(32) = 528 < 1024
         }
     }
     if (wave == 0) {   // normalise the start
@@ -961,16 +987,15 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
         for (int t = tid; t < nact0 * S * KM; t += MASTER_THREADS) {
             const int l = t % KM, j = (t / KM) % S, a = t / (KM * S);
             const int o = L.act[a + MASTER_PACT], k = L.kk[j];
+            if (l >= k) continue;
             double acc = 0.0;
-            if (l < k) {
-                const double *T = L.TACT + (size_t)a * N * LDN;
-                const double *B = L.BLK + ((size_t)j * n_out + o) * KE;
-                for (int l2 = 0; l2 < k; l2++) {
-                    const int lo = l < l2 ? l : l2, hi = l < l2 ? l2 : l;
-                    acc = fma(B[sym_e(lo, hi, k)], T[(size_t)L.idx[j * KM + l2] * LDN + 0], acc);
-                }
+            const double *T = L.TACT + (size_t)a * N * LDN;
+            const double *B = master_blk(L, n_out, j, o);
+            for (int l2 = 0; l2 < k; l2++) {
+                const int lo = l < l2 ? l : l2, hi = l < l2 ? l2 : l;
+                acc = fma(B[sym_e(lo, hi, k)], T[(size_t)L.idx[j * KM + l2] * LDN + 0], acc);
             }
-            L.AAC[t] = acc;
+            master_aac(L, a, j)[l] = acc;
         }
         __syncthreads();
         for (int t = tid; t < S * nact0; t += MASTER_THREADS) {
@@ -978,7 +1003,8 @@ __global__ __launch_bounds__(MASTER_THREADS) void k_master_newton(MasterArgs A)
             const int o = L.act[a + MASTER_PACT], k = L.kk[j];
             const double *T = L.TACT + (size_t)a * N * LDN;
             double acc = 0.0;
-            for (int l = 0; l < k; l++) acc = fma(L.AAC[((size_t)a * S + j) * KM + l], T[(size_t)L.idx[j * KM + l] * LDN + 0], acc);
+            const double *aj = master_aac(L, a, j);
+            for (int l = 0; l < k; l++) acc = fma(aj[l], T[(size_t)L.idx[j * KM + l] * LDN + 0], acc);
             const double ro = L.r[o];
             L.GQ[j * MASTER_PACT + a] = -(1.0 - A.eps_bg) * L.cc[j] * acc / A.s[o] / (ro * ro);
         }
@@ -1386,12 +1412,24 @@ static int master_lds_limit(int dev)
 // Which instantiation runs a problem, and the largest support it holds.  Up to 32 models the register tiles 12 / 20 / 26 / 32.
 // Beyond: 40 / 48 / 64 in registers (one evaluation's elimination 3 us instead of 150 in LDS) when the larger Phi stride (nt + 2
 // instead of N + 1) still leaves the support the natural layout would allow, or N + 16 entries; else the LDS eliminations (nt = 0).
-static int master_choose_nt(int dev, int N, int n_out, int KM, int *s_max)
+// The support is modelled as S groups of kb models of which min(nw, S) have kw (> kb) models instead.
+struct SupportShape {
+    int kb, kw, nw;
+    int km(int S) const { return (nw > 0 && S > 0) ? kw : kb; }
+    int sum_ke(int S) const { const int w = std::min(nw, S); return (S - w) * (kb * (kb + 1) / 2) + w * (kw * (kw + 1) / 2); }
+    int sum_k(int S) const { const int w = std::min(nw, S); return (S - w) * kb + w * kw; }
+};
+static size_t master_lds_shape(int N, int n_out, int S, const SupportShape &sh, int nt)
+{
+    return master_lds_bytes(N, n_out, S, sh.km(S), nt, sh.sum_ke(S), sh.sum_k(S));
+}
+
+static int master_choose_nt(int dev, int N, int n_out, const SupportShape &sh, int *s_max)
 {
     const size_t limit = (size_t)master_lds_limit(dev) - MASTER_STATIC_LDS;
     auto fit = [&](int nt) {
         int S = MASTER_SMAX;
-        while (S > 0 && master_lds_bytes(N, n_out, S, KM, nt) > limit) S -= 2;
+        while (S > 0 && master_lds_shape(N, n_out, S, sh, nt) > limit) S -= 2;
         return S;
     };
     int nt = N <= 12 ? 12 : N <= 20 ? 20 : N <= 26 ? 26 : N <= 32 ? 32 : 0;
@@ -1410,7 +1448,17 @@ extern "C" int bluest_master_max_support(bluest_plan_t plan, int *s_max)
     if (!plan || !s_max) return fail(BLUEST_ERR_ARG, "null pointer");
     if (!plan->finalized) return fail(BLUEST_ERR_STATE, "plan not finalized");
     int rc = require_gpu(); if (rc) return rc;
-    (void)master_choose_nt(plan->device, plan->N, (int)plan->outs.size(), plan->kmax, s_max);     // 0: this problem does not fit the single-workgroup master
+    // plans of groups up to 16 models: every support entry counted at the widest size.  Wider groups (up to BLUEST_MAX_GROUP): the
+    // support is sized for entries of the widest size <= 16 the plan has plus MASTER_WIDE_IN_SUPPORT groups of its widest size, so
+    // one or two wide groups leave the usual support limit; a support with more of them that does not fit is refused at launch
+    SupportShape sh{plan->kmax, plan->kmax, 0};
+    if (plan->kmax > MASTER_KB_MAX) {
+        sh.kb = 1;
+        for (const auto &od : plan->outs)
+            for (int k = 1; k <= std::min(od.K, MASTER_KB_MAX); k++) if (od.sizes[k - 1] > 0) sh.kb = std::max(sh.kb, k);
+        sh.nw = MASTER_WIDE_IN_SUPPORT;
+    }
+    (void)master_choose_nt(plan->device, plan->N, (int)plan->outs.size(), sh, s_max);     // 0: this problem does not fit the single-workgroup master
     return BLUEST_OK;
 }
 
@@ -1485,8 +1533,15 @@ static int master_launch(bluest_plan_t plan, int S, const int64_t *support_host,
         if (!found) return fail(BLUEST_ERR_ARG, "group %lld belongs to no output", (long long)gi);
         KM = std::max(KM, kk[j]);
     }
-    const int nt = master_choose_nt(plan->device, N, n_out, KM, nullptr);
-    const size_t lds = master_lds_bytes(N, n_out, S, KM, nt);
+    SupportShape sh{KM, KM, 0};
+    int sumKE = 0, sumK = 0;
+    for (int j = 0; j < S; j++) { sumKE += kk[j] * (kk[j] + 1) / 2; sumK += kk[j]; }
+    if (KM > MASTER_KB_MAX) {
+        sh.kb = 1; sh.nw = 0;
+        for (int j = 0; j < S; j++) { if (kk[j] > MASTER_KB_MAX) sh.nw++; else sh.kb = std::max(sh.kb, (int)kk[j]); }
+    }
+    const int nt = master_choose_nt(plan->device, N, n_out, sh, nullptr);
+    const size_t lds = master_lds_bytes(N, n_out, S, KM, nt, sumKE, sumK);
     const int lds_limit = master_lds_limit(plan->device) - MASTER_STATIC_LDS;
     if (lds > (size_t)lds_limit) return fail(BLUEST_ERR_ARG, "master problem needs %zu bytes of LDS (limit %d)", lds, lds_limit);
     idx.assign((size_t)S * KM, 0);
@@ -1522,7 +1577,7 @@ static int master_launch(bluest_plan_t plan, int S, const int64_t *support_host,
     HIP_TRY(hipStreamSynchronize(st));                    // the staging vector dies with this call
     unsigned char *d = (unsigned char *)plan->d_master;
     MasterArgs A;
-    A.N = N; A.n_out = n_out; A.S = S; A.KM = KM;
+    A.N = N; A.n_out = n_out; A.S = S; A.KM = KM; A.sumKE = sumKE; A.sumK = sumK;
     A.eps_bg = eps_bg; A.tol = tol; A.act_tol = 1.0e-3; A.floor_x = 1.0e-6; A.maxit = maxit;
     A.fb = eps_bg > 0.0 ? 0.0 : 0.9;       // without the background V has kinks where a model drops out: stay inside the face
     A.invcov = (const double *const *)d;

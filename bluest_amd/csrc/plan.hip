@@ -681,7 +681,7 @@ static int plan_add_common(bluest_plan_t plan, int K, const int64_t *sizes, cons
 {
     if (!plan) return fail(BLUEST_ERR_ARG, "plan is NULL");
     if (plan->finalized) return fail(BLUEST_ERR_STATE, "plan already finalized");
-    if (K <= 0 || K > BLUEST_MAX_GROUP) return fail(BLUEST_ERR_ARG, "K=%d out of range (1..%d)", K, BLUEST_MAX_GROUP);
+    if (K <= 0 || K > BLUEST_MAX_GROUP) return fail(BLUEST_ERR_ARG, "K=%d out of range (1..%d): groups hold at most BLUEST_MAX_GROUP = %d models", K, BLUEST_MAX_GROUP, BLUEST_MAX_GROUP);
     if (!sizes || !groups) return fail(BLUEST_ERR_ARG, "null pointer");
     if ((int)plan->outs.size() >= 32767) return fail(BLUEST_ERR_ARG, "too many outputs");
     od.K = K;
@@ -1650,6 +1650,29 @@ extern "C" int bluest_plan_is_identity(bluest_plan_t plan, int *yes)
     return BLUEST_OK;
 }
 
+// widest group the multiplicative tail of the fused solve + gradient kernel handles (its unrolled tile paths), 0: plan does not qualify
+static int eval_ma_kmax(const bluest_plan_s *plan)
+{
+    if (plan->outs.size() != 1 || !plan->identity || plan->gate) return 0;
+    return plan->matfree ? 8 : 12;
+}
+
+extern "C" int bluest_plan_eval_ma_kmax(bluest_plan_t plan, int *kmax)
+{
+    if (!plan || !kmax) return fail(BLUEST_ERR_ARG, "null pointer");
+    if (!plan->finalized) return fail(BLUEST_ERR_STATE, "plan not finalized");
+    *kmax = eval_ma_kmax(plan);
+    return BLUEST_OK;
+}
+
+extern "C" int bluest_plan_kmax(bluest_plan_t plan, int *kmax)
+{
+    if (!plan || !kmax) return fail(BLUEST_ERR_ARG, "null pointer");
+    if (!plan->finalized) return fail(BLUEST_ERR_STATE, "plan not finalized");
+    *kmax = plan->kmax;
+    return BLUEST_OK;
+}
+
 // phase 1 of the second-order finish on a single-output plan: one evaluation of m_dev whose fused solve + gradient kernel applies the
 // multiplicative update to x_dev / m_dev itself (no gradient array, no third launch); var / status as bluest_plan_eval leaves them
 extern "C" int bluest_plan_eval_ma(bluest_plan_t plan, double *m_dev, double *var_dev, int32_t *status_dev, const double *s_dev,
@@ -1657,8 +1680,9 @@ extern "C" int bluest_plan_eval_ma(bluest_plan_t plan, double *m_dev, double *va
 {
     if (!plan || !m_dev || !var_dev || !status_dev || !s_dev || !cc_dev || !x_dev) return fail(BLUEST_ERR_ARG, "null pointer");
     if (!plan->finalized) return fail(BLUEST_ERR_STATE, "plan not finalized");
-    if (plan->outs.size() != 1 || !plan->identity || plan->gate || plan->kmax > (plan->matfree ? 8 : 12))
-        return fail(BLUEST_ERR_STATE, "bluest_plan_eval_ma: one output on all groups under the identity mapping only");
+    if (plan->outs.size() != 1 || !plan->identity || plan->gate || plan->kmax > eval_ma_kmax(plan))
+        return fail(BLUEST_ERR_STATE, "bluest_plan_eval_ma: one output on all groups under the identity mapping only, groups of at most %d models",
+                    eval_ma_kmax(plan));
     // (the gradient pointer only selects the fused kernel: with the tail on, nothing is written through it)
     return plan_eval(plan, m_dev, 1, 0, 0.0, var_dev, plan->d_v, plan->grad_len, status_dev, stream, nullptr, 0, nullptr, MaTail{x_dev, cc_dev, m_dev, s_dev});
 }

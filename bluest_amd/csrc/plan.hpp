@@ -159,7 +159,7 @@ __device__ __forceinline__ void grad_tile(const TileDesc &td, const double *__re
     }
 }
 
-// generic k (13..16): slots re-read per candidate, no big register arrays
+// generic k (13..BLUEST_MAX_GROUP): slots re-read per candidate, no big register arrays
 __device__ __forceinline__ void grad_tile_generic(const TileDesc &td, const double *__restrict__ tvals, const double *__restrict__ v,
                                                   const int32_t *__restrict__ status, int N, int n_out, int n_cand,
                                                   double *__restrict__ grad, int64_t grad_stride, int lane)

@@ -35,7 +35,7 @@ extern "C" {
 #define BLUEST_ERR_STATE   4   /* plan not finalized / already finalized */
 
 #define BLUEST_MAX_MODELS  64  /* n  (Phi is n x n) */
-#define BLUEST_MAX_GROUP   16  /* k_max */
+#define BLUEST_MAX_GROUP   32  /* k_max: largest group a plan or bluest_group_pinv takes */
 
 /* per-(candidate,output) evaluation status written by bluest_plan_solve / bluest_plan_eval */
 #define BLUEST_EVAL_OK         0
@@ -82,7 +82,8 @@ int bluest_hessKQ(double *hess_hd, int N, int k, int q, int64_t Lk, int64_t Lq, 
 
 /* replaces the per-group numpy.linalg.pinv(C[g,g]) loop of SAP.__init__ (bluest/sap.py:69-79):
  * invcov_i = pinv(C[g_i,g_i]) (symmetric eigen-decomposition, cut-off 1e-15*max|lambda| as numpy's default
- * rcond), flattened C-order (Lk*k*k). */
+ * rcond), flattened C-order (Lk*k*k).  1 <= k <= BLUEST_MAX_GROUP: one thread per group up to 16 models, one wavefront per group
+ * (block and eigenvectors in LDS) for 17..32; BLUEST_ERR_STATE if a group's Jacobi sweeps do not converge. */
 int bluest_group_pinv(const double *C_hd, int N, int k, int64_t Lk, const int64_t *groupsk_hd,
                       double *invcovsk_hd);
 
@@ -108,7 +109,7 @@ int bluest_plan_destroy(bluest_plan_t plan);
 int bluest_capture_guard(int on);
 int bluest_deferred_plans(int *count);
 
-/* Add output o (call once per output, in order).  K = max group size of this output; sizes[k-1] = L_k for
+/* Add output o (call once per output, in order).  K = max group size of this output (1..BLUEST_MAX_GROUP); sizes[k-1] = L_k for
  * k = 1..K; groups = concat_k (L_k*k) model indices; invcovs = concat_k (L_k*k*k) (HOST pointers, copied);
  * mapping = L_o global indices (m_o = m[mapping]) or NULL for the identity (requires L_o == L_global). */
 int bluest_plan_add_output(bluest_plan_t plan, int K, const int64_t *sizes, const int64_t *groups,
@@ -147,7 +148,8 @@ int bluest_plan_traffic(bluest_plan_t plan, int64_t *phi_bytes, int64_t *grad_by
 /* MATRIX-FREE evaluation (csrc/matfree.hip; the form BASELINE.json's north star names): the inverse of every group's covariance
  * block (bluest/sap.py:69-79) is recomputed in registers where bluest/cmisc.cpp:25-40,58-72 read the stored one, so an evaluation
  * reads the groups' model indices and m only.  Chosen at bluest_plan_finalize for plans that qualify (outputs given by their
- * covariance, group sizes <= 8, <= 48 models, every block safely positive definite) when BLUEST_MATFREE=1, or on its own when the
+ * covariance, group sizes <= 8 (MF_KMAX), <= 48 models, every block safely positive definite; a plan with any wider group, up to
+ * BLUEST_MAX_GROUP, always evaluates on stored inverses, whatever their size) when BLUEST_MATFREE=1, or on its own when the
  * stored streams exceed 64 MB; single-candidate bluest_plan_eval / bluest_plan_phi / bluest_plan_solve_grad then take it.
  * The GRADIENT pass alone is matrix-free on every plan that qualifies (BLUEST_MATFREE=2 forces exactly that, 0 forbids everything): the
  * stored Phi pass is then followed by one kernel that folds its partials, solves and recomputes the group factors for the gradient.
@@ -363,6 +365,12 @@ int bluest_ma_update(bluest_plan_t plan, const double *var_dev, const int32_t *s
 int bluest_plan_is_identity(bluest_plan_t plan, int *yes);      /* every output on all groups, local index = global index */
 int bluest_plan_eval_ma(bluest_plan_t plan, double *m_dev, double *var_dev, int32_t *status_dev, const double *s_dev,
                         const double *cc_dev, double *x_dev, void *stream);
+/* *kmax = the widest group bluest_plan_eval_ma accepts on this plan: 12 on stored inverses, 8 under matrix-free evaluation, 0 when
+ * the plan does not qualify at all (more than one output, not the identity mapping, or gated).  A plan whose widest group exceeds
+ * it (a finalized plan's widest group: bluest_plan_kmax) steps phase 1 with bluest_plan_eval + bluest_ma_update instead. */
+int bluest_plan_eval_ma_kmax(bluest_plan_t plan, int *kmax);
+/* *kmax = the widest group over all outputs of a finalized plan (<= BLUEST_MAX_GROUP) */
+int bluest_plan_kmax(bluest_plan_t plan, int *kmax);
 /* m_i = cc_i ((1 - eps) x_S[i in S] + eps / L); sup_dev ascending */
 int bluest_support_point(int64_t L, int S, const int64_t *sup_dev, const double *xs_dev, const double *cc_dev, double eps,
                          double *m_dev, void *stream);
