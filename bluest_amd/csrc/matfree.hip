@@ -27,8 +27,12 @@
 #include "plan.hpp"
 
 #define MF_KMAX 8
+#define MF_NMAX 48                             // widest plan (models) mf_finalize accepts
 #define MF_TILE_WAVES 15                       // tile wavefronts of k_solve_grad_mf (+ the solving one)
 static const int64_t MF_AUTO_BYTES = 64ll << 20;
+using MfKuSet = InstSet<5, 6, 8>;              // KU of k_solve_grad_mf
+using MfNwSet = InstSet<4, 8>;                 // NW of k_phi_matfree
+static int mf_nw(int N) { return N <= 32 ? 8 : 4; }
 
 struct MfTile {            // 64 consecutive groups of one size of one output (8 bytes: one scalar load)
     int32_t first;         // local index (within the output) of the first group
@@ -522,11 +526,11 @@ int mf_finalize(bluest_plan_t plan)
     if (mode < 0 && plan->phi_bytes + plan->grad_bytes < MF_AUTO_BYTES) return BLUEST_OK;
     const bool full = mode != 2;
     const int n_out = (int)plan->outs.size(), N = plan->N;
-    if (N > 48 || n_out < 1) return BLUEST_OK;      // (LDS of k_solve_grad_mf: the elimination's matrix + the covariance)
+    if (N > MF_NMAX || n_out < 1) return BLUEST_OK;      // (LDS of k_solve_grad_mf: the elimination's matrix + the covariance)
     for (const auto &od : plan->outs) if (od.h_C.size() != (size_t)N * N || od.K > MF_KMAX || !od.d_groups) return BLUEST_OK;
     MfState *S = new MfState();
     S->nsym = N * (N + 1) / 2;
-    S->nw = N <= 32 ? 8 : 4;
+    S->nw = mf_nw(N);
     // tiles
     std::vector<MfTile> tiles;
     S->tile_begin.assign(n_out + 1, 0);
@@ -665,7 +669,7 @@ int mf_solve_grad(bluest_plan_t plan, const double *rec_dev, double delta, doubl
     if (!S) return fail(BLUEST_ERR_STATE, "matrix-free state missing");
     const MfArgs A = mf_args(plan);
     const dim3 grid((unsigned)S->wgs_grad);
-    nt_dispatch(plan->N, [&](auto nt) { dispatch_le<5, 6, 8>(plan->kmax, [&](auto ku) {
+    nt_dispatch(plan->N, [&](auto nt) { MfKuSet::dispatch(plan->kmax, [&](auto ku) {
         hipLaunchKernelGGL((k_solve_grad_mf<decltype(nt)::value, decltype(ku)::value>), grid, dim3(64 * (MF_TILE_WAVES + 1)), S->lds_grad, st, A,
                            rec_dev, delta, plan->d_rows, plan->fold_reg, plan->d_partial, S->d_wg_begin, S->bpo, var_dev, plan->d_v, status_dev, grad_dev, ma);
     }); });
@@ -690,6 +694,23 @@ extern "C" int bluest_plan_matfree(bluest_plan_t plan, int *matfree, int64_t *mf
         *mf_bytes = b;
     }
     return BLUEST_OK;
+}
+
+// launch configuration query (bluest_plan_launch_config): the instantiations mf_phi_record / mf_solve_grad launch on this plan
+void mf_instantiation(bluest_plan_t plan, int32_t *nw, int32_t *nt, int32_t *ku)
+{
+    const MfState *S = reinterpret_cast<const MfState *>(plan->mf);
+    *nw = S ? S->nw : 0;
+    *nt = pick_nt(plan->N);
+    MfKuSet::dispatch(plan->kmax, [&](auto k) { *ku = decltype(k)::value; });
+}
+
+// ... and the sets they come from, within what mf_finalize accepts (N <= MF_NMAX, k <= MF_KMAX)
+void mf_instantiation_set(int axis, std::vector<int32_t> &s)
+{
+    if (axis == BLUEST_LC_MF_NW) for (int n = 1; n <= MF_NMAX; n++) { if (std::find(s.begin(), s.end(), mf_nw(n)) == s.end()) s.push_back(mf_nw(n)); }
+    if (axis == BLUEST_LC_MF_NT) for (int v : NtSet::values) { if (v <= pick_nt(MF_NMAX)) s.push_back(v); }
+    if (axis == BLUEST_LC_MF_KU) for (int v : MfKuSet::values) { if (v <= MF_KMAX) s.push_back(v); }
 }
 
 // gradient of this plan's groups from given v / status (one candidate)

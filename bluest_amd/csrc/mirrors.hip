@@ -412,6 +412,9 @@ static int objectiveK_impl(double *PHI, int N, int k, int64_t Lk, const MT *mk, 
     int nblocks = (int)std::min<int64_t>((Lk + 255) / 256, 1024);
     double *slabs = nullptr;
     HIP_TRY(hipMalloc((void **)&slabs, (size_t)nblocks * NN * sizeof(double)));
+    // dynamic LDS beyond the default (N > 78; 128 KiB at N = 128) needs the attribute, as for k_phi_matfree in matfree.hip
+    if ((size_t)NN * sizeof(double) > (48u << 10))
+        (void)hipFuncSetAttribute((const void *)k_objectiveK<MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(NN * sizeof(double)));
     hipLaunchKernelGGL((k_objectiveK<MT>), dim3(nblocks), dim3(256), NN * sizeof(double), 0, slabs, N, k, Lk, s_m.dev, s_g.dev, s_ic.dev);
     hipLaunchKernelGGL(k_fold_slabs, dim3((NN + 255) / 256), dim3(256), 0, 0, s_phi.dev, slabs, NN, nblocks);
     hipError_t e = hipGetLastError();

@@ -370,7 +370,10 @@ __global__ __launch_bounds__(256) void k_grad_tiles(const TileDesc *__restrict__
 // tiles per workgroup of the fused kernel: wavefront 0 solves, wavefronts 1..TPB own one tile each.  15 (1024 threads,
 // 128 VGPRs) while the register-resident matrix (2 NT VGPRs) and tile (KU (KU+1) + KU VGPRs) fit, else 7 (512 threads, 256 VGPRs)
 __host__ __device__ constexpr int fused_tpb(int NT, int KU) { return (NT <= 26 && KU <= 8) ? 15 : 7; }
-template <class F> static void solve_grad_ku_dispatch(int kmax, F &&launch) { dispatch_le<5, 6, 8, 12>(kmax, launch); }   // KU of k_solve_grad
+using SolveGradKuSet = InstSet<5, 6, 8, 12>;     // KU of k_solve_grad
+using GradTilesKuSet = InstSet<5, 8, 12>;        // KU of k_grad_tiles
+using PhiObSet = InstSet<2, 4, 8>;               // OB of k_phi_chunks_shared (phi_ob)
+template <class F> static void solve_grad_ku_dispatch(int kmax, F &&launch) { SolveGradKuSet::dispatch(kmax, launch); }
 template <int NT, int KU>
 __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int N, int n_out, const RowDesc *__restrict__ rows, int nsym, FoldReg reg,
                                                     const double2 *__restrict__ partial, const double *__restrict__ rec, double delta,
@@ -1440,7 +1443,7 @@ extern "C" int bluest_plan_phi_len(bluest_plan_t plan, int64_t *len)
 static void launch_grad(bluest_plan_t plan, const double *v_dev, const int32_t *status_dev, int n_cand, double *grad_dev,
                         int64_t grad_stride, hipStream_t st)
 {
-    dispatch_le<5, 8, 12>(plan->kmax, [&](auto ku) {
+    GradTilesKuSet::dispatch(plan->kmax, [&](auto ku) {
         hipLaunchKernelGGL((k_grad_tiles<decltype(ku)::value>), dim3((unsigned)((plan->n_tiles + 3) / 4)), dim3(256), 0, st, plan->d_tiles,
                            plan->n_tiles, plan->d_tvals, v_dev, status_dev, plan->N, (int)plan->outs.size(), n_cand, grad_dev, grad_stride, plan->gate);
     });
@@ -1472,23 +1475,35 @@ static void launch_solve_grad(bluest_plan_t plan, const double *rec, double delt
     }); });
 }
 
+// outputs per wavefront of the shared Phi pass (k_phi_chunks_shared<OB>), 0: the plain k_phi_chunks.  Sharing the column stream
+// saves bytes, but the pass is latency-bound, so keep at least ~4096 wavefronts in flight (measured at n=20, n_out=8: OB=8 6.9 us,
+// OB=4 5.5 us, OB=2 5.1 us, OB=1 6.1 us): the widest OB of PhiObSet that does, else the narrowest
+static int phi_ob(const bluest_plan_s *p)
+{
+    const int n_out = (int)p->outs.size();
+    if (!p->shared || n_out < 2) return 0;
+    const int64_t ncpo = p->n_chunks / n_out;
+    for (int i = PhiObSet::count - 1; i > 0; i--) {
+        const int ob = PhiObSet::values[i];
+        if (ob <= n_out && ncpo * ((n_out + ob - 1) / ob) >= 4096) return ob;
+    }
+    return PhiObSet::values[0];
+}
+
 static void launch_chunks(bluest_plan_t p, const double *m, int n_cand, int64_t m_stride, hipStream_t st)
 {
     const int n_out = (int)p->outs.size();
     // one wavefront per workgroup of the chunk kernels (WPB = 1): single-wavefront workgroups drain earliest at the kernel's end
     // (same-box A/B at the headline size, two runs each: step 12.86 / 12.26 / 12.05 us with 4 / 2 / 1 wavefronts, 13.8 with 16)
-    if (p->shared && n_out >= 2) {
+    if (const int ob = phi_ob(p)) {
         const int64_t ncpo = p->n_chunks / n_out;
-        // outputs per wavefront: sharing the column stream saves bytes, but the pass is latency-bound, so keep at least
-        // ~4096 wavefronts in flight (measured at n=20, n_out=8: OB=8 6.9 us, OB=4 5.5 us, OB=2 5.1 us, OB=1 6.1 us)
-        int ob = 8;
-        while (ob > 2 && (ncpo * ((n_out + ob - 1) / ob) < 4096 || ob > n_out)) ob /= 2;
-#define LCS2(OB, COLT) hipLaunchKernelGGL((k_phi_chunks_shared<OB, 1, COLT>), dim3((unsigned)ncpo, (n_out + OB - 1) / OB), dim3(64), 0, st, \
+        PhiObSet::dispatch(ob, [&](auto obc) {
+            constexpr int OB = decltype(obc)::value;
+#define LCS2(COLT) hipLaunchKernelGGL((k_phi_chunks_shared<OB, 1, COLT>), dim3((unsigned)ncpo, (n_out + OB - 1) / OB), dim3(64), 0, st, \
                                    p->d_vals, reinterpret_cast<const COLT *>(p->d_cols), p->iters, ncpo, n_out, m, m_stride, n_cand, p->partial_stride, p->d_pslot, p->slots_per_output, p->d_partial, p->gate)
-#define LCS(OB) do { if (p->cols16) LCS2(OB, uint16_t); else LCS2(OB, int32_t); } while (0)
-        if (ob == 8) LCS(8); else if (ob == 4) LCS(4); else LCS(2);
-#undef LCS
+            if (p->cols16) LCS2(uint16_t); else LCS2(int32_t);
 #undef LCS2
+        });
         return;
     }
 #define LPC(COLT) hipLaunchKernelGGL((k_phi_chunks<1, COLT>), dim3((unsigned)p->n_chunks), dim3(64), 0, st, p->d_vals, \
@@ -1540,8 +1555,11 @@ extern "C" int bluest_plan_solve_pinv(bluest_plan_t plan, const double *phi_dev,
     int rc = plan_ready(plan, n_cand); if (rc) return rc;
     if (!phi_dev || !var_dev || !v_dev || !status_dev) return fail(BLUEST_ERR_ARG, "null pointer");
     const int n_out = (int)plan->outs.size(), N = plan->N;
-    hipLaunchKernelGGL(k_pinv_from_record, dim3(n_out, n_cand), dim3(64), (size_t)2 * N * (N + 1) * sizeof(double),
-                       (hipStream_t)stream, N, n_out, phi_dev, delta, var_dev, v_dev, status_dev);
+    const size_t lds = (size_t)2 * N * (N + 1) * sizeof(double);      // 66 560 bytes at N = 64
+    // dynamic LDS beyond the default needs the attribute (per device, as for k_phi_matfree in matfree.hip)
+    if (lds > (48u << 10)) (void)hipFuncSetAttribute((const void *)k_pinv_from_record, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k_pinv_from_record, dim3(n_out, n_cand), dim3(64), lds, (hipStream_t)stream, N, n_out, phi_dev, delta, var_dev,
+                       v_dev, status_dev);
     HIP_TRY(hipGetLastError());
     return BLUEST_OK;
 }
@@ -1670,6 +1688,55 @@ extern "C" int bluest_plan_kmax(bluest_plan_t plan, int *kmax)
     if (!plan || !kmax) return fail(BLUEST_ERR_ARG, "null pointer");
     if (!plan->finalized) return fail(BLUEST_ERR_STATE, "plan not finalized");
     *kmax = plan->kmax;
+    return BLUEST_OK;
+}
+
+// the instantiation every kernel family of an evaluation takes on this plan, from the helpers the launchers call (phi_ob, the
+// InstSet dispatchers, fused_tpb, fold_threads, mf_instantiation)
+extern "C" int bluest_plan_launch_config(bluest_plan_t plan, int n_cand, int32_t *cfg)
+{
+    if (!plan || !cfg) return fail(BLUEST_ERR_ARG, "null pointer");
+    if (!plan->finalized) return fail(BLUEST_ERR_STATE, "plan not finalized");
+    if (n_cand <= 0 || n_cand > plan->max_cand) return fail(BLUEST_ERR_ARG, "n_cand=%d outside 1..%d", n_cand, plan->max_cand);
+    std::fill(cfg, cfg + BLUEST_LC_COUNT, 0);
+    const bool one = n_cand == 1 && !plan->gate;
+    cfg[BLUEST_LC_PATH] = (one && plan->matfree) ? 2 : (one && plan->mf_gradient) ? 3 : (n_cand == 1) ? 1 : 0;
+    cfg[BLUEST_LC_PHI_OB] = phi_ob(plan);
+    cfg[BLUEST_LC_COLS16] = plan->cols16 ? 1 : 0;
+    nt_dispatch(plan->N, [&](auto nt) {
+        cfg[BLUEST_LC_NT] = decltype(nt)::value;
+        cfg[BLUEST_LC_FOLD_THREADS] = fold_threads(decltype(nt)::value);
+        solve_grad_ku_dispatch(plan->kmax, [&](auto ku) {
+            cfg[BLUEST_LC_SOLVE_GRAD_KU] = decltype(ku)::value;
+            cfg[BLUEST_LC_FUSED_TPB] = fused_tpb(decltype(nt)::value, decltype(ku)::value);
+        });
+    });
+    cfg[BLUEST_LC_TILES_PER_WG] = plan->fused_tpb;
+    GradTilesKuSet::dispatch(plan->kmax, [&](auto ku) { cfg[BLUEST_LC_GRAD_TILES_KU] = decltype(ku)::value; });
+    cfg[BLUEST_LC_MATFREE] = plan->matfree ? 1 : (plan->mf_gradient ? 2 : 0);
+    if (plan->mf_gradient) mf_instantiation(plan, &cfg[BLUEST_LC_MF_NW], &cfg[BLUEST_LC_MF_NT], &cfg[BLUEST_LC_MF_KU]);
+    cfg[BLUEST_LC_ITERS] = plan->iters;
+    cfg[BLUEST_LC_KMAX] = plan->kmax;
+    return BLUEST_OK;
+}
+
+extern "C" int bluest_launch_set(int axis, int32_t *values, int cap, int *n)
+{
+    if (!n || (cap > 0 && !values)) return fail(BLUEST_ERR_ARG, "null pointer");
+    std::vector<int32_t> s;
+    auto add = [&](int v) { if (std::find(s.begin(), s.end(), v) == s.end()) s.push_back(v); };
+    switch (axis) {
+    case BLUEST_LC_PHI_OB: for (int v : PhiObSet::values) add(v); break;
+    case BLUEST_LC_NT: for (int v : NtSet::values) add(v); break;
+    case BLUEST_LC_FOLD_THREADS: for (int v : NtSet::values) add(fold_threads(v)); break;
+    case BLUEST_LC_SOLVE_GRAD_KU: for (int v : SolveGradKuSet::values) add(v); break;
+    case BLUEST_LC_FUSED_TPB: for (int nt : NtSet::values) for (int ku : SolveGradKuSet::values) add(fused_tpb(nt, ku)); break;
+    case BLUEST_LC_GRAD_TILES_KU: for (int v : GradTilesKuSet::values) add(v); break;
+    case BLUEST_LC_MF_NW: case BLUEST_LC_MF_NT: case BLUEST_LC_MF_KU: mf_instantiation_set(axis, s); break;
+    default: return fail(BLUEST_ERR_ARG, "axis %d has no instantiation set", axis);
+    }
+    *n = (int)s.size();
+    for (int i = 0; i < (int)s.size() && i < cap; i++) values[i] = s[(size_t)i];
     return BLUEST_OK;
 }
 

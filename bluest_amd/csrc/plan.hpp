@@ -202,3 +202,5 @@ int mf_phi_record(bluest_plan_t plan, const double *m_dev, double *rec_dev, cons
 int mf_solve_grad(bluest_plan_t plan, const double *rec_dev, double delta, double *var_dev, int32_t *status_dev, double *grad_dev, hipStream_t st,
                   MaTail ma = MaTail{nullptr, nullptr, nullptr, nullptr});
 int mf_grad(bluest_plan_t plan, const double *v_dev, const int32_t *status_dev, double *grad_dev, hipStream_t st);
+void mf_instantiation(bluest_plan_t plan, int32_t *nw, int32_t *nt, int32_t *ku);
+void mf_instantiation_set(int axis, std::vector<int32_t> &s);

@@ -474,7 +474,15 @@ inline void dispatch_le(int x, F &&launch)
     if constexpr (sizeof...(VS) > 0) { if (x > V) return dispatch_le<VS...>(x, launch); }
     launch(std::integral_constant<int, V>{});
 }
-// the register-array size NT >= N
-template <class F> inline void nt_dispatch(int N, F &&launch) { dispatch_le<8, 12, 16, 20, 26, 32, 48, 64>(N, launch); }
+// one instantiation axis of a kernel family: dispatch() picks as dispatch_le does; values[] is the set the library is built with
+// (bluest_launch_set reports it, so tests ask which instantiations exist instead of restating them)
+template <int... VS>
+struct InstSet {
+    static constexpr int count = sizeof...(VS);
+    static constexpr int values[count] = {VS...};
+    template <class F> static void dispatch(int x, F &&launch) { dispatch_le<VS...>(x, launch); }
+};
+using NtSet = InstSet<8, 12, 16, 20, 26, 32, 48, 64>;     // the register-array size NT >= N
+template <class F> inline void nt_dispatch(int N, F &&launch) { NtSet::dispatch(N, launch); }
 
 static inline int pick_nt(int N) { int nt = 0; nt_dispatch(N, [&](auto v) { nt = v; }); return nt; }

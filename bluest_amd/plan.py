@@ -14,6 +14,25 @@ from ._lib import check, ptr
 
 EVAL_OK, EVAL_INF, EVAL_NO_MODEL0, EVAL_SINGULAR = 0, 1, 2, 3
 
+# BLUEST_LC_* of include/bluest_hip.h, in index order
+LAUNCH_FIELDS = ("path", "phi_ob", "cols16", "nt", "fold_threads", "solve_grad_ku", "fused_tpb", "tiles_per_wg", "grad_tiles_ku",
+                 "matfree", "mf_nw", "mf_nt", "mf_ku", "iters", "kmax")
+# axes with an instantiation set (bluest_launch_set)
+LAUNCH_AXES = ("phi_ob", "nt", "fold_threads", "solve_grad_ku", "fused_tpb", "grad_tiles_ku", "mf_nw", "mf_nt", "mf_ku")
+
+
+def launch_sets():
+    """dict axis -> list of the values the library is built with along it (host only: no GPU needed)"""
+    L = _lib.lib()
+    out = {}
+    for axis in LAUNCH_AXES:
+        n = ctypes.c_int(0)
+        check(L.bluest_launch_set(LAUNCH_FIELDS.index(axis), None, 0, ctypes.byref(n)))
+        vals = np.zeros(n.value, dtype=np.int32)
+        check(L.bluest_launch_set(LAUNCH_FIELDS.index(axis), ptr(vals), n.value, ctypes.byref(n)))
+        out[axis] = [int(v) for v in vals]
+    return out
+
 
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -291,6 +310,13 @@ class Plan(object):
             else:
                 G[o, np.asarray(mp, dtype=np.int64)] = gh[self.grad_off[o]:self.grad_off[o] + len(mp)]
         return G
+
+    def launch_config(self, n_cand=1):
+        """dict: the kernel instantiation every family of an evaluation of n_cand candidates takes on this plan
+        (include/bluest_hip.h, bluest_plan_launch_config; keys are LAUNCH_FIELDS)"""
+        cfg = np.zeros(len(LAUNCH_FIELDS), dtype=np.int32)
+        check(self.lib.bluest_plan_launch_config(self._h, int(n_cand), ptr(cfg)))
+        return dict(zip(LAUNCH_FIELDS, (int(x) for x in cfg)))
 
     def phi_matrix(self, m, delta=0.0):
         """Phi(m) + delta*I for every output as an (n_cand, n_out, N, N) device tensor (misc.py:459-461)"""

@@ -371,6 +371,30 @@ int bluest_plan_eval_ma(bluest_plan_t plan, double *m_dev, double *var_dev, int3
 int bluest_plan_eval_ma_kmax(bluest_plan_t plan, int *kmax);
 /* *kmax = the widest group over all outputs of a finalized plan (<= BLUEST_MAX_GROUP) */
 int bluest_plan_kmax(bluest_plan_t plan, int *kmax);
+/* Launch configuration (read-only, host only): the kernel instantiation each family of an evaluation of n_cand candidates takes on
+ * this plan, decided by the same helpers the launchers call.  cfg receives BLUEST_LC_COUNT entries, indexed by BLUEST_LC_*: */
+#define BLUEST_LC_PATH           0   /* bluest_plan_eval: 0 Phi pass + fold/solve + k_grad_tiles, 1 Phi pass + fused k_solve_grad,
+                                        2 k_phi_matfree + k_solve_grad_mf, 3 stored Phi pass + k_solve_grad_mf */
+#define BLUEST_LC_PHI_OB         1   /* stored Phi pass: 0 plain k_phi_chunks, else OB of k_phi_chunks_shared */
+#define BLUEST_LC_COLS16         2   /* 1: uint16 column indices, 0: int32 */
+#define BLUEST_LC_NT             3   /* NT of the fold + solve kernels */
+#define BLUEST_LC_FOLD_THREADS   4   /* their workgroup size */
+#define BLUEST_LC_SOLVE_GRAD_KU  5   /* KU of k_solve_grad */
+#define BLUEST_LC_FUSED_TPB      6   /* tile wavefronts per workgroup of that instantiation */
+#define BLUEST_LC_TILES_PER_WG   7   /* tiles per workgroup the plan launches it with (follows the device's compute units) */
+#define BLUEST_LC_GRAD_TILES_KU  8   /* KU of k_grad_tiles */
+#define BLUEST_LC_MATFREE        9   /* as bluest_plan_matfree */
+#define BLUEST_LC_MF_NW         10   /* NW of k_phi_matfree (0: no matrix-free state) */
+#define BLUEST_LC_MF_NT         11   /* NT of k_solve_grad_mf */
+#define BLUEST_LC_MF_KU         12   /* KU of k_solve_grad_mf */
+#define BLUEST_LC_ITERS         13   /* 256-entry blocks per chunk of the stored Phi pass */
+#define BLUEST_LC_KMAX          14
+#define BLUEST_LC_COUNT         15
+int bluest_plan_launch_config(bluest_plan_t plan, int n_cand, int32_t *cfg);
+/* the instantiation set the library is built with along one axis (BLUEST_LC_PHI_OB, _NT, _FOLD_THREADS, _SOLVE_GRAD_KU, _FUSED_TPB,
+ * _GRAD_TILES_KU, _MF_NW, _MF_NT, _MF_KU; the matrix-free ones within what a matrix-free plan may have): *n values, the first
+ * min(*n, cap) of them into values */
+int bluest_launch_set(int axis, int32_t *values, int cap, int *n);
 /* m_i = cc_i ((1 - eps) x_S[i in S] + eps / L); sup_dev ascending */
 int bluest_support_point(int64_t L, int S, const int64_t *sup_dev, const double *xs_dev, const double *cc_dev, double eps,
                          double *m_dev, void *stream);
