@@ -144,6 +144,17 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__
 // fused: fold chunk partials + solve.  grid = (n_out, n_cand), block = fold_threads (fold) -> wavefront 0 (solve).
 // want_v: bit0 = also produce v (gradient wanted); bit1 / bit2 = diagnostics (fold only / solve twice)
 // that the library does not set.
+// The gate of a launch whose tail may REWRITE that gate (the line-search decision's enable output is the same word): it is read
+// once per workgroup and handed to every thread through LDS, so a workgroup is on or off as a whole -- a wavefront that read
+// the word after the decision's store could otherwise run the tile code on LDS its solving wavefront never filled.
+__device__ __forceinline__ bool gate_closed(const int32_t *gate, int *s_closed)
+{
+    if (!gate) return false;
+    if (threadIdx.x == 0) *s_closed = __hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 ? 1 : 0;
+    __syncthreads();
+    return *s_closed != 0;
+}
+
 template <int NT>
 __global__ __launch_bounds__(fold_threads(NT)) void k_solve_from_chunks(int N, int n_out, const RowDesc *__restrict__ rows, int nsym, FoldReg reg,
                                                            const double2 *__restrict__ partial, int64_t n_chunks,
@@ -154,10 +165,14 @@ __global__ __launch_bounds__(fold_threads(NT)) void k_solve_from_chunks(int N, i
 {
     __shared__ SolveLds<NT> lds;
     __shared__ double spg_ls[SPG_STATE_DOUBLES];
+    __shared__ int s_closed;
     const int o = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
-    if (gate && *gate == 0) {   // device-side predication (SPG line-search slots)
-        // the line-search decision still has to close the slot (it sets the gate of the finishing launches on the last one)
-        if (spg_state && o == 0 && c == 0 && tid < WAVE) spg_decide_wave(spg_state, var, status, n_out, last_slot, spg_enable, spg_ls, tid);
+    if (gate_closed(gate, &s_closed)) {   // device-side predication (SPG line-search slots)
+        // the line-search decision still has to close the slot (it sets the gate of the finishing launches on the last one).
+        // Its enable output IS the gate, so it may only write once every workgroup of this launch has read the gate: they take a
+        // ticket of their own (ticket[16]) and the last one to arrive decides.
+        if (spg_state && tid < WAVE && spg_closed_last(ticket + 16, gridDim.x * gridDim.y, tid))
+            spg_decide_wave(spg_state, var, status, n_out, last_slot, spg_enable, spg_ls, tid);
         return;
     }
     SpgPrefetch pf;
@@ -390,17 +405,25 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
     __shared__ SolveLds<NT> lds;
     __shared__ double spg_ls[SPG_STATE_DOUBLES];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    if (gate && *gate == 0) {
-        // predicated off; the line-search decision still has to close the slot (see k_solve_from_chunks)
-        if (spg_state && blockIdx.x == 0 && wave == 0) spg_decide_wave(spg_state, var, status, n_out, last_slot, spg_enable, spg_ls, lane);
-        return;
-    }
     const int64_t t0 = (int64_t)blockIdx.x * tpb;      // tpb <= FUSED_TPB tiles per workgroup (wavefronts beyond it only fold)
     // which output, and am I its first workgroup: arithmetic when every output has the same number of workgroups (bpo > 0,
     // the usual case), else from the first tile's descriptor (one more dependent load in front of the fold)
     int o, first;
     if (bpo > 0) { o = blockIdx.x / bpo; first = (blockIdx.x % bpo) == 0; }
     else { const TileDesc td0 = tiles[t0]; o = td0.out; first = (td0.n_valid >> 30) & 1; }
+    __shared__ int s_closed;
+    if (gate_closed(gate, &s_closed)) {
+        // predicated off; the line-search decision still has to close the slot (see k_solve_from_chunks): the first workgroups
+        // of the n_out outputs -- the ones that publish V and status and take the decision ticket when the gate is open -- arrive
+        // at a ticket of their own, and the last one decides, so none of THEM can see the gate the decision reopens.  A whole
+        // workgroup that is not the first of its output may start after that store and run: it folds the Phi partials of the
+        // accepted trial (the predicated-off Phi pass of this slot left them alone), so it rewrites that trial's gradient
+        // entries with the same bits.  The other way round (a rejected last slot closes the gate under an open launch) a late
+        // workgroup skips gradient entries of a trial nobody uses.
+        if (spg_state && first && wave == 0 && spg_closed_last(ticket + 16, (unsigned int)n_out, lane))
+            spg_decide_wave(spg_state, var, status, n_out, last_slot, spg_enable, spg_ls, lane);
+        return;
+    }
     SpgPrefetch pf;
     if (spg_state && first && wave == 0) spg_prefetch_state(spg_state, lane, pf);   // in flight during the fold (spg_state.hpp)
     if (N < NT) { clear_pads(lds, N, tid, NTHREADS); __syncthreads(); }   // uniform; every real entry is written by the fold

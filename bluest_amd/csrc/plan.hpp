@@ -77,7 +77,8 @@ struct bluest_plan_s {
     void *d_scratch = nullptr;   // set-up scratch of bluest_plan_add_output_cov (C, groups, inverses), reused across outputs
     size_t scratch_bytes = 0;
     int32_t *d_status = nullptr; // workspace for eval when caller passes NULL
-    unsigned int *d_ticket = nullptr;   // arrival counter of the fused solve + line-search decision (bluest_plan_eval_decide)
+    unsigned int *d_ticket = nullptr;   // [0] arrival counter of the fused solve + line-search decision (bluest_plan_eval_decide);
+                                        // [16] arrival counter of the workgroups of a predicated-off launch that still decides
     // second-order finish (newton.hip): descriptor blob of the master problem (plain hipMalloc, grown on demand) and the
     // host-side global -> local group maps it is built from
     // matrix-free evaluation (matfree.hip): chosen at finalize for plans that qualify

@@ -163,6 +163,19 @@ __device__ __forceinline__ void spg_decide_wave(double *__restrict__ st, const d
     }
 }
 
+// Predicated-off launch that still has to decide: arrival ticket of the workgroups that read the gate closed (one wavefront each;
+// nothing is published, the decision reads only what earlier launches wrote).  True, uniformly, in the last one to arrive.
+__device__ __forceinline__ bool spg_closed_last(unsigned int *closed_ticket, unsigned int n_arrivals, int lane)
+{
+    int last = 0;
+    if (lane == 0) {
+        const unsigned int t = __hip_atomic_fetch_add(closed_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = (t == n_arrivals - 1u) ? 1 : 0;
+        if (last) __hip_atomic_store(closed_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next launch
+    }
+    return __builtin_amdgcn_readfirstlane(last) != 0;
+}
+
 // the decision without an early prefetch (stand-alone kernel, predicated-off launches)
 __device__ __forceinline__ void spg_decide_wave(double *__restrict__ st, const double *var, const int32_t *status, int n_out,
                                                 int last_slot, int32_t *__restrict__ enable, double *ls, int lane)
