@@ -28,6 +28,14 @@ constexpr int MAXL = BLUEST_MFMC_MAX_NEIGHBOURS + 1;      // models in a clique,
 constexpr double LB_MARGIN_MIN = 1e-9;
 constexpr double LB_MARGIN_ULPS = 16.0;
 constexpr int64_t CAND_CAP = 1 << 16;                      // cliques rounded per window
+// Counting scans the window loop may spend between two windows that round a clique.  A window that rounds something consumes
+// cliques, and there are at most 2^30; a window that comes out empty (the halving overshot below the next lower bound v) at
+// least halves the distance from lo to v, and the next one needs one more halving to get there.  From hi - lo down to the
+// spacing of doubles at v that is E <= log2((hi - lo) / v) + 53 empty windows of 1, 2, ..., E halvings, E^2/2 scans in all.
+// Lower and upper bounds of one problem are sample costs or errors of the same models: a range of 2^30 between them gives
+// E <= 83 and fewer than 3500 scans.  Only lower bounds of exactly zero (|rho_1| = 1: more than CAND_CAP cliques at LB = 0,
+// lo = -1 halving towards them for 1074 windows, some 5e5 scans) need more, and they end in the same message either way.
+constexpr int MAX_IDLE_SCANS = 4096;
 
 struct Prob {
     int nb, n_out, budget_mode, continuous, small_budget, integer_round;
@@ -547,7 +555,9 @@ extern "C" int bluest_mfmc_search(int nb, int n_out, int flags, double budget, c
         if (hs[2] > 0.0) { *status = BLUEST_MFMC_TOO_BIG; return BLUEST_OK; }
         const double U = hs[0], LBmax = hs[1];
         double lo = -1.0, best = INFINITY;
+        int idle = 0;                                   // counting scans since a window last rounded a clique
         auto count_in = [&](int pass, double a, double b, unsigned long long *out) -> int {
+            if (pass == 2) idle++;
             HIP_TRY(hipMemsetAsync(cnt, 0, 8, st));
             hipLaunchKernelGGL(k_mfmc_scan, dim3(grid), dim3(BLK), 0, st, P, pass, total, a, b, partf, partm, stats, cnt, cand);
             HIP_TRY(hipGetLastError());
@@ -569,6 +579,9 @@ extern "C" int bluest_mfmc_search(int nb, int n_out, int flags, double budget, c
             }
             if (!(T > lo) || c > (unsigned long long)CAND_CAP)     // the window cannot advance: never loop on it
                 return fail(BLUEST_ERR_STATE, "more than %lld cliques share one lower bound", (long long)CAND_CAP);
+            if (idle >= MAX_IDLE_SCANS)                             // checked once per window, halvings included
+                return fail(BLUEST_ERR_STATE, "%d counting scans without a clique to round: the lower bounds cluster too "
+                            "closely for windows of %lld (more than that many share one lower bound)", idle, (long long)CAND_CAP);
             if (c > 0) {
                 if ((rc = count_in(3, lo, T, &c))) return rc;
                 c = std::min(c, (unsigned long long)CAND_CAP);
@@ -579,6 +592,7 @@ extern "C" int bluest_mfmc_search(int nb, int n_out, int flags, double budget, c
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipMemcpyAsync(&best, bf, 8, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipStreamSynchronize(st));
+                idle = 0;
             }
             lo = T;
         }
