@@ -76,7 +76,7 @@ __device__ bool proj(const Params &P, const double *in, double *out, Lds &L, boo
     const int Mp = M + (M & 1);              // padded to even: the pad index is never coupled, its rotations are identities
     const int h = Mp / 2;
     __syncthreads();                         // `in` was written by other threads
-    double nrm = 0.0;
+    double amax = 0.0;
     for (int idx = tid; idx < Mp * Mp; idx += BLK) {
         const int i = idx / Mp, j = idx % Mp;
         double a = 0.0;
@@ -86,10 +86,19 @@ __device__ bool proj(const Params &P, const double *in, double *out, Lds &L, boo
         }
         L.A[i * LD + j] = a;
         L.V[i * LD + j] = (i == j) ? 1.0 : 0.0;
-        nrm += a * a;
+        amax = fmax(amax, fabs(a));
     }
-    nrm = block_sum(nrm, L.red);             // its barriers also publish A and V
-    const double tol = JACOBI_TOL * sqrt(nrm);
+    amax = block_max(amax, L.red);           // its barriers also publish A and V
+    // ||A||_F = max|a| * sqrt(sum (a / max|a|)^2): a plain sum of a^2 is inf from entries of 1.4e154 on, and an infinite
+    // tolerance would skip every rotation and report convergence
+    double nrm = 0.0;
+    if (amax > 0.0)
+        for (int idx = tid; idx < Mp * Mp; idx += BLK) {
+            const double a = L.A[(idx / Mp) * LD + idx % Mp] / amax;
+            nrm += a * a;
+        }
+    nrm = block_sum(nrm, L.red);
+    const double tol = JACOBI_TOL * amax * sqrt(nrm);
     bool converged = false;
     for (int sweep = 0; sweep < MAX_SWEEPS && !converged; sweep++) {
         if (tid == 0) L.rotated = 0;

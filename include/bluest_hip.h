@@ -439,7 +439,10 @@ int bluest_mfmc_search(int nb, int n_out, int flags, double budget, const double
 /* ---------------------------------------------------------------------------------------------------------
  * Part 8 -- projection of the covariances onto the SPD matrices (bluest/blue_models.py:348-433, SPG of bluest/spg.py:39-132)
  * Host arrays, n_out outputs of M x M row-major float64: C (NaN allowed where mask is 0), mask (1 = entry known, 0 = not
- * coupled).  Per output, one workgroup of ONE launch:
+ * coupled).  A mask entry may be any finite weight m, of either sign; two thresholds apply to it, as in the reference:
+ *   |m| < 1e-14   the entry is unknown: C is read as 0 there (NaN and Inf allowed), and one such entry selects SPG;
+ *   m^2 < 1e-15   the entry weighs nothing in f and in the gradient (m = 1e-8 is known AND weighs nothing).
+ * Per output, one workgroup of ONE launch:
  *   - every mask entry nonzero: X = V max(l, spd_threshold) V^T with (l, V) = eigh of the lower triangle of C, f = ||C - X||_F,
  *     gpmax = it = count = 0 (the reference's single clip);
  *   - otherwise SPG on f(X) = 1/2 ||mask^2 o (X - C)||^2 with proj(X) = the clip of (X + X^T)/2, started at proj(mask o C),
