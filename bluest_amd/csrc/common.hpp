@@ -43,6 +43,9 @@ int launch_group_pinv_u8(const double *dC, int N, int k, int64_t Lk, const uint8
 // ------------------------------------------------------------------------------------------------------
 #define WAVE 64
 
+// The __shfl_xor butterflies below compile to ds_bpermute_b32: two per double and level, six dependent trips through the LDS
+// crossbar per reduction.  They stay for callers that may run under divergent control flow.  Where all 64 lanes are evidently
+// active, the *_dpp forms further down pair the same lanes in the same order without touching the LDS.
 __device__ __forceinline__ double wave_sum(double x)
 {   // fixed xor-butterfly: every lane ends with the same, order-independent-of-timing sum
 #pragma unroll
@@ -62,3 +65,92 @@ __device__ __forceinline__ long long wave_sum_ll(long long x)
     return x;
 }
 
+// ---- the same pairing tree (lane l with l^32, l^16, l^8, l^4, l^2, l^1, in that order) on the VALU: no LDS crossbar ----
+// A 64-bit value travels as its two dwords.  IEEE addition and fmax are commutative, so whichever lane of a pair holds which
+// operand the pair ends with the same bits, exactly those of the butterfly above.  ALL 64 LANES MUST BE ACTIVE for the wave forms
+// (quad_x1 / quad_x2 only need the lane's whole quad).
+struct Dw2 { int lo, hi; };
+__device__ __forceinline__ Dw2 dw2(double x) { return Dw2{__double2loint(x), __double2hiint(x)}; }
+__device__ __forceinline__ Dw2 dw2(long long x) { return Dw2{(int)(unsigned long long)x, (int)((unsigned long long)x >> 32)}; }
+__device__ __forceinline__ void from_dw2(Dw2 w, double &x) { x = __hiloint2double(w.hi, w.lo); }
+__device__ __forceinline__ void from_dw2(Dw2 w, long long &x) { x = (long long)(((unsigned long long)(unsigned)w.hi << 32) | (unsigned)w.lo); }
+
+// DPP move of every lane: CTRL 0x4E = quad_perm:[2,3,0,1] (l^2), 0xB1 = quad_perm:[1,0,3,2] (l^1), 0x128 = row_ror:8 (l^8)
+template <int CTRL, class T>
+__device__ __forceinline__ T dpp_all(T x)
+{
+    const Dw2 w = dw2(x);
+    Dw2 r;
+    r.lo = __builtin_amdgcn_update_dpp(w.lo, w.lo, CTRL, 0xf, 0xf, false);
+    r.hi = __builtin_amdgcn_update_dpp(w.hi, w.hi, CTRL, 0xf, 0xf, false);
+    T y; from_dw2(r, y); return y;
+}
+template <class T> __device__ __forceinline__ T quad_x1(T x) { return dpp_all<0xB1>(x); }
+template <class T> __device__ __forceinline__ T quad_x2(T x) { return dpp_all<0x4E>(x); }
+template <class T> __device__ __forceinline__ T row_x8(T x) { return dpp_all<0x128>(x); }
+// l^4: row_ror:n hands lane i of a 16-lane row the value of lane (i - n) mod 16, so the lanes with bit 2 clear (banks 0 and 2,
+// bank_mask 0x5) take row_ror:12 and the lanes with bit 2 set (banks 1 and 3, bank_mask 0xa) take row_ror:4
+template <class T>
+__device__ __forceinline__ T row_x4(T x)
+{
+    const Dw2 w = dw2(x);
+    Dw2 r;
+    r.lo = __builtin_amdgcn_update_dpp(w.lo, w.lo, 0x12C, 0xf, 0x5, false);
+    r.lo = __builtin_amdgcn_update_dpp(r.lo, w.lo, 0x124, 0xf, 0xa, false);
+    r.hi = __builtin_amdgcn_update_dpp(w.hi, w.hi, 0x12C, 0xf, 0x5, false);
+    r.hi = __builtin_amdgcn_update_dpp(r.hi, w.hi, 0x124, 0xf, 0xa, false);
+    T y; from_dw2(r, y); return y;
+}
+// l^32 / l^16: v_permlane32_swap exchanges the upper half of its first operand with the lower half of its second (v_permlane16_swap:
+// the odd rows of the first with the even rows of the second).  With the same value in both, every lane ends with its own value
+// in one result and its partner's in the other; which is which depends on the half (row), and the commutative `op` need not know.
+template <class T, class Op>
+__device__ __forceinline__ T swap32_combine(T x, Op op)
+{
+    const Dw2 w = dw2(x);
+    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)w.lo, (unsigned)w.lo, false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)w.hi, (unsigned)w.hi, false, false);
+    T a, b;
+    from_dw2(Dw2{(int)lo[0], (int)hi[0]}, a);
+    from_dw2(Dw2{(int)lo[1], (int)hi[1]}, b);
+    return op(a, b);
+}
+template <class T, class Op>
+__device__ __forceinline__ T swap16_combine(T x, Op op)
+{
+    const Dw2 w = dw2(x);
+    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)w.lo, (unsigned)w.lo, false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)w.hi, (unsigned)w.hi, false, false);
+    T a, b;
+    from_dw2(Dw2{(int)lo[0], (int)hi[0]}, a);
+    from_dw2(Dw2{(int)lo[1], (int)hi[1]}, b);
+    return op(a, b);
+}
+struct OpAdd { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; } };
+struct OpFmax { __device__ __forceinline__ double operator()(double a, double b) const { return fmax(a, b); } };
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce_dpp(T x, Op op)
+{
+    x = swap32_combine(x, op);
+    x = swap16_combine(x, op);
+    x = op(x, row_x8(x));
+    x = op(x, row_x4(x));
+    x = op(x, quad_x2(x));
+    x = op(x, quad_x1(x));
+    return x;
+}
+__device__ __forceinline__ double wave_sum_dpp(double x) { return wave_reduce_dpp(x, OpAdd()); }
+__device__ __forceinline__ double wave_max_dpp(double x) { return wave_reduce_dpp(x, OpFmax()); }
+__device__ __forceinline__ long long wave_sum_ll_dpp(long long x) { return wave_reduce_dpp(x, OpAdd()); }
+
+// A kernel argument the entry block must already hold in scalar registers.  The compiler otherwise sinks each argument's scalar
+// load to the block of its first use, behind every early-out branch: one dependent round trip to the kernarg segment per group of
+// arguments before the first useful load.  Named here together, the arguments arrive in one batch behind one wait.
+// (This steers the compiler, it is not a guarantee: profiles/r06_isa_counts.txt records the entry blocks it gave; no test holds them.)
+template <class T> __device__ __forceinline__ void kernarg_now(const T &x) { asm volatile("" ::"s"(x)); }
+template <class T, class... R> __device__ __forceinline__ void kernarg_now(const T &x, const R &...rest) { kernarg_now(x); kernarg_now(rest...); }
+// A wave-uniform word nobody writes while this kernel runs, read with a scalar load.  (The compiler takes a volatile statement
+// such as kernarg_now for a store to anything, and a plain load behind one becomes a vector load with a vector wait.)
+__device__ __forceinline__ int32_t uniform_word(const int32_t *p) { return *(const __attribute__((address_space(4))) int32_t *)p; }
+// a lane value the optimiser must take as it is HERE: keeps a load's first use (and its wait) where the code puts it
+template <class T> __device__ __forceinline__ T lane_value_here(T x) { asm volatile("" : "+v"(x)); return x; }

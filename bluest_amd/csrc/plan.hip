@@ -55,6 +55,15 @@ template <> __device__ __forceinline__ int4 load_cols4<uint16_t>(const uint16_t 
     return make_int4((int)(w.x & 0xffffu), (int)(w.x >> 16), (int)(w.y & 0xffffu), (int)(w.y >> 16));
 }
 // Phi pass: one wavefront per chunk of CH = 256*iters entries; lane l owns entries [4l, 4l+4) of each 256-block.
+// Prologue of both chunk kernels: the arguments are pinned into one batch (kernarg_now), the gate word costs one more scalar
+// wait, and the slot of the chunk's partial -- needed by the final store only -- is loaded without a branch (a plan without a slot
+// table reads a dummy word and keeps the chunk number), so no wait stands between the launch and the first streaming load.
+// Tail: every workgroup is whole wavefronts and the early exits are wave-uniform, so all 64 lanes reach the reductions, which
+// run on the VALU (wave_sum_dpp / wave_max_dpp, common.hpp).
+// The slot word of a plan without a slot table is a dummy read of the first four bytes of the column stream (always there: the
+// plan has at least one chunk); its value is discarded, only the absence of a branch around the load matters.
+// What the compiler makes of this prologue is recorded in profiles/r06_isa_counts.txt: re-check it there after a toolchain update.
+__device__ __forceinline__ bool phi_gate_closed(const int32_t *gate) { return gate && uniform_word(gate) == 0; }
 template <int WPB, typename COLT>
 __global__ __launch_bounds__(64 * WPB) void k_phi_chunks(const double *__restrict__ vals, const COLT *__restrict__ cols,
                                                     int iters, int64_t n_chunks, const double *__restrict__ m,
@@ -62,11 +71,14 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks(const double *__restric
                                                     const int32_t *__restrict__ pslot, int64_t pstride,
                                                     const int32_t *__restrict__ gate)
 {
-    if (gate && *gate == 0) return;   // device-side predication (SPG line-search slots)
+    kernarg_now(vals, cols, iters, n_chunks, m, m_stride, n_cand, partial, pslot, pstride, gate);
+    const bool closed = phi_gate_closed(gate);      // device-side predication (SPG line-search slots)
     const int64_t chunk = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
+    // where the fold expects this chunk's partial (in flight until the store; the address is valid whatever chunk is)
+    const int32_t slot_ld = *(pslot && chunk < n_chunks ? pslot + chunk : reinterpret_cast<const int32_t *>(cols));
+    if (closed) return;
     if (chunk >= n_chunks) return;
-    const int64_t slot = pslot ? (int64_t)pslot[chunk] : chunk;      // where the fold expects this chunk's partial
     const int64_t base = chunk * (int64_t)iters * 256 + lane * 4;
     for (int c = 0; c < n_cand; c++) {
         const double *mc = m + (int64_t)c * m_stride;
@@ -82,8 +94,9 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks(const double *__restric
             s = fma(v23.y, m3, s);
             amax = fmax(fmax(amax, fmax(fabs(m0), fabs(m1))), fmax(fabs(m2), fabs(m3)));
         }
-        s = wave_sum(s);
-        amax = wave_max(amax);
+        s = wave_sum_dpp(s);
+        amax = wave_max_dpp(amax);
+        const int64_t slot = pslot ? (int64_t)lane_value_here(slot_ld) : chunk;      // the slot load's only wait
         if (lane == 0) partial[(int64_t)c * pstride + slot] = make_double2(s, amax);
     }
 }
@@ -97,13 +110,17 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__
                                                            int64_t m_stride, int n_cand, int64_t pstride, const int32_t *__restrict__ pslot,
                                                            int slots_per_output, double2 *__restrict__ partial, const int32_t *__restrict__ gate)
 {
-    if (gate && *gate == 0) return;   // device-side predication (SPG line-search slots)
+    kernarg_now(vals, cols, iters, ncpo, n_out, m, m_stride, n_cand, pstride, pslot, slots_per_output, partial, gate);
+    const bool closed = phi_gate_closed(gate);      // device-side predication (SPG line-search slots)
     const int64_t chunk = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const int o0 = blockIdx.y * OB;
+    // where the fold expects this chunk's partials: output-major chunk numbering, or the regular rows' slots (one structure for
+    // all outputs).  In flight until the stores; the address is valid whatever chunk is.
+    const int32_t slot_ld = *(pslot && chunk < ncpo ? pslot + chunk : reinterpret_cast<const int32_t *>(cols));
+    if (closed) return;
     if (chunk >= ncpo) return;
-    // where the fold expects this chunk's partials: output-major chunk numbering, or the regular rows' slots (one structure for all outputs)
-    const int64_t slot = pslot ? (int64_t)pslot[chunk] : chunk, ostride = pslot ? (int64_t)slots_per_output : ncpo;
+    const int64_t ostride = pslot ? (int64_t)slots_per_output : ncpo;
     const int64_t CH = (int64_t)iters * 256;
     const int64_t base = chunk * CH + lane * 4;
     for (int c = 0; c < n_cand; c++) {
@@ -132,10 +149,13 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__
                 s[oo] = fma(v23[oo].y, m3, s[oo]);
             }
         }
-        amax = wave_max(amax);
+        amax = wave_max_dpp(amax);
+        const int64_t slot = pslot ? (int64_t)lane_value_here(slot_ld) : chunk;      // the slot load's only wait
+        // (the OB sums one behind the other, each stored as it is ready: reducing them as interleaved chains with the stores
+        //  afterwards measured no faster once they were DPP chains, profiles/r06_step_parts_ablation.txt)
 #pragma unroll
         for (int oo = 0; oo < OB; oo++) {
-            const double t = wave_sum(s[oo]);
+            const double t = wave_sum_dpp(s[oo]);
             if (lane == 0 && o0 + oo < n_out) partial[(int64_t)c * pstride + (int64_t)(o0 + oo) * ostride + slot] = make_double2(t, amax);
         }
     }
@@ -166,6 +186,8 @@ __global__ __launch_bounds__(fold_threads(NT)) void k_solve_from_chunks(int N, i
     __shared__ SolveLds<NT> lds;
     __shared__ double spg_ls[SPG_STATE_DOUBLES];
     __shared__ int s_closed;
+    // everything in front of the fold's first load arrives in one batch (kernarg_now, common.hpp)
+    kernarg_now(N, n_out, rows, nsym, reg.Cd, reg.Co, reg.rank_ab, partial, n_chunks, gate, spg_state);
     const int o = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
     if (gate_closed(gate, &s_closed)) {   // device-side predication (SPG line-search slots)
         // the line-search decision still has to close the slot (it sets the gate of the finishing launches on the last one).
@@ -229,6 +251,7 @@ __global__ __launch_bounds__(fold_threads(NT)) void k_fold_to_record(int N, int 
                                                         double *__restrict__ rec)
 {
     __shared__ SolveLds<NT> lds;
+    kernarg_now(N, n_out, rows, nsym, reg.Cd, reg.Co, reg.rank_ab, partial, n_chunks, rec);      // one batch (common.hpp)
     const int o = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
     fold_rows(lds, N, rows, o * nsym, nsym, partial + (int64_t)c * n_chunks, tid, fold_threads(NT), reg);
     __syncthreads();
@@ -404,6 +427,9 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
     constexpr int PU = tile_pairs(KU);
     __shared__ SolveLds<NT> lds;
     __shared__ double spg_ls[SPG_STATE_DOUBLES];
+    // everything in front of the fold's first load arrives in one batch (kernarg_now, common.hpp); the tile stream's arguments
+    // and the outputs may follow while the fold is in flight
+    kernarg_now(N, n_out, rows, nsym, reg.Cd, reg.Co, reg.rank_ab, partial, rec, tiles, bpo, tpb, gate, spg_state);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int64_t t0 = (int64_t)blockIdx.x * tpb;      // tpb <= FUSED_TPB tiles per workgroup (wavefronts beyond it only fold)
     // which output, and am I its first workgroup: arithmetic when every output has the same number of workgroups (bpo > 0,

@@ -80,7 +80,8 @@ __device__ __forceinline__ double fast_max(double v)
 // fold chunk partials of rows [row_begin, row_begin+n_rows) into lds.phi / lds.amax; all threads of the block.
 // FOUR adjacent lanes share a row: lane q sums chunks q, q+4, q+8, ... (up to 8 independent loads in flight, so a row of
 // <= 32 chunks costs ONE memory round trip), then the quad combines as (s0+s1)+(s2+s3) -- a fixed order, so the result
-// is deterministic and identical in every kernel that folds.  nthreads must be a multiple of 4.
+// is deterministic and identical in every kernel that folds -- with quad_perm DPP moves (common.hpp; the lanes of a quad share
+// their row, so a quad is active as a whole).  nthreads must be a multiple of 4.
 // (Staging one output's partials in LDS first -- one coalesced copy, then the fold out of LDS -- was measured and rejected:
 //  step 15.7 vs 15.3 us at the headline size; the LDS round trip and the extra barrier cost more than the dependent HBM
 //  round trip descriptor -> partials they replace.)
@@ -119,10 +120,10 @@ __device__ __forceinline__ void fold_rows(SolveLds<NT> &lds, int N, const RowDes
                 for (int i = 0; i < 8; i++) { s += v[i].x; am = fmax(am, v[i].y); }
             }
             const int a = (int)(ab & 0xffu), b = (int)(ab >> 8);
-            s += __shfl_xor(s, 1);
-            am = fmax(am, __shfl_xor(am, 1));
-            s += __shfl_xor(s, 2);
-            am = fmax(am, __shfl_xor(am, 2));
+            s += quad_x1(s);
+            am = fmax(am, quad_x1(am));
+            s += quad_x2(s);
+            am = fmax(am, quad_x2(am));
             if (q == 0) {
                 lds.at(a, b) = s;
                 lds.at(b, a) = s;
@@ -143,10 +144,10 @@ __device__ __forceinline__ void fold_rows(SolveLds<NT> &lds, int N, const RowDes
 #pragma unroll
             for (int i = 0; i < 8; i++) { s += v[i].x; am = fmax(am, v[i].y); }
         }
-        s += __shfl_xor(s, 1);
-        am = fmax(am, __shfl_xor(am, 1));
-        s += __shfl_xor(s, 2);
-        am = fmax(am, __shfl_xor(am, 2));
+        s += quad_x1(s);
+        am = fmax(am, quad_x1(am));
+        s += quad_x2(s);
+        am = fmax(am, quad_x2(am));
         if (q == 0) {
             lds.at(rd.a, rd.b) = s;
             lds.at(rd.b, rd.a) = s;

@@ -395,6 +395,12 @@ int bluest_plan_launch_config(bluest_plan_t plan, int n_cand, int32_t *cfg);
  * _GRAD_TILES_KU, _MF_NW, _MF_NT, _MF_KU; the matrix-free ones within what a matrix-free plan may have): *n values, the first
  * min(*n, cap) of them into values */
 int bluest_launch_set(int axis, int32_t *values, int cap, int *n);
+/* Diagnostic: the cross-lane reductions of csrc/common.hpp that do not use the LDS crossbar, seen lane by lane.  One wavefront per
+ * row of 64 doubles of in_dev (n_rows x 64); every output is n_rows x 64 and holds what EACH lane ends with: sum_dev the wave sum,
+ * max_dev the wave maximum, quad_dev the sum over the lane's quad in the fold's order ((l^1) first, then (l^2)), isum_dev
+ * (int64) the integer wave sum of the rows' bit patterns shifted right by 8 (so that nothing overflows). */
+int bluest_wave_reduce_probe(const double *in_dev, int64_t n_rows, double *sum_dev, double *max_dev, double *quad_dev,
+                             int64_t *isum_dev, void *stream);
 /* m_i = cc_i ((1 - eps) x_S[i in S] + eps / L); sup_dev ascending */
 int bluest_support_point(int64_t L, int S, const int64_t *sup_dev, const double *xs_dev, const double *cc_dev, double eps,
                          double *m_dev, void *stream);
