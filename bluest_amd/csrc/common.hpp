@@ -58,11 +58,26 @@ __device__ __forceinline__ double wave_max(double x)
     for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_xor(x, off, WAVE));
     return x;
 }
+__device__ __forceinline__ double wave_min(double x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x = fmin(x, __shfl_xor(x, off, WAVE));
+    return x;
+}
 __device__ __forceinline__ long long wave_sum_ll(long long x)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, WAVE);
     return x;
+}
+
+// single-wavefront LDS ordering: LDS operations of one wave execute in order; this only stops the compiler from
+// moving LDS accesses across it and drains lgkmcnt
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
 // ---- the same pairing tree (lane l with l^32, l^16, l^8, l^4, l^2, l^1, in that order) on the VALU: no LDS crossbar ----

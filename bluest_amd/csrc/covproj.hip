@@ -3,14 +3,14 @@
 //
 // One workgroup per output, one launch for all outputs; the whole SPG loop runs inside the workgroup.  A projection
 //   proj(X) = V max(l, thr) V^T,   (l, V) = eigh((X + X^T) / 2)
-// is a parallel-ordered cyclic Jacobi eigendecomposition in LDS (round-robin pairing: M/2 disjoint rotations per step, M-1
-// steps per sweep, sweeps until a whole sweep rotates nothing), accurate to ~eps ||X|| whatever the eigenvalue order.  The
+// is a parallel-ordered cyclic Jacobi eigendecomposition in LDS (jacobi.hpp; round-robin pairing: M/2 disjoint rotations per step,
+// M-1 steps per sweep, sweeps until a whole sweep rotates nothing), accurate to ~eps ||X|| whatever the eigenvalue order.  The
 // matrix and its eigenvectors (two 64 x 65 float64 arrays, 65 KB) live in LDS; the SPG vectors (x, g, d, trial point, ...) in
 // the workgroup's own slice of global scratch.
 //
 // The branches that decide the trajectory (nonmonotone Armijo acceptance, safeguarded interpolation, the sdoty <= 0 case, the
 // stopping test) follow the reference expression by expression (float64, no contraction).
-#include "common.hpp"
+#include "jacobi.hpp"
 
 #pragma clang fp contract(off)
 
@@ -21,8 +21,6 @@ constexpr int NWAVE = BLK / WAVE;
 constexpr int MAXM = BLUEST_MAX_MODELS;
 constexpr int LD = MAXM + 1;                 // LDS row stride (doubles)
 constexpr int HALF = MAXM / 2;
-constexpr int MAX_SWEEPS = 40;
-constexpr double JACOBI_TOL = 1e-18;         // a rotation is skipped when |a_pq| <= JACOBI_TOL * ||A||_F
 constexpr int NVEC = 8;                      // global scratch vectors per output
 
 struct Params {
@@ -74,7 +72,6 @@ __device__ bool proj(const Params &P, const double *in, double *out, Lds &L, boo
 {
     const int M = P.M, N = M * M, tid = threadIdx.x;
     const int Mp = M + (M & 1);              // padded to even: the pad index is never coupled, its rotations are identities
-    const int h = Mp / 2;
     __syncthreads();                         // `in` was written by other threads
     double amax = 0.0;
     for (int idx = tid; idx < Mp * Mp; idx += BLK) {
@@ -89,83 +86,14 @@ __device__ bool proj(const Params &P, const double *in, double *out, Lds &L, boo
         amax = fmax(amax, fabs(a));
     }
     amax = block_max(amax, L.red);           // its barriers also publish A and V
-    // ||A||_F = max|a| * sqrt(sum (a / max|a|)^2): a plain sum of a^2 is inf from entries of 1.4e154 on, and an infinite
-    // tolerance would skip every rotation and report convergence
-    double nrm = 0.0;
+    double nrm = 0.0;                        // sum (a / max|a|)^2: see jacobi_tol
     if (amax > 0.0)
         for (int idx = tid; idx < Mp * Mp; idx += BLK) {
             const double a = L.A[(idx / Mp) * LD + idx % Mp] / amax;
             nrm += a * a;
         }
     nrm = block_sum(nrm, L.red);
-    const double tol = JACOBI_TOL * amax * sqrt(nrm);
-    bool converged = false;
-    for (int sweep = 0; sweep < MAX_SWEEPS && !converged; sweep++) {
-        if (tid == 0) L.rotated = 0;
-        for (int r = 0; r < Mp - 1; r++) {
-            if (tid < h) {                   // round-robin pairing: (r, Mp-1) and (r+k, r-k) mod (Mp-1)
-                int a, b;
-                if (tid == 0) { a = r; b = Mp - 1; }
-                else          { a = (r + tid) % (Mp - 1); b = (r - tid + (Mp - 1)) % (Mp - 1); }
-                const int p = min(a, b), q = max(a, b);
-                const double apq = L.A[p * LD + q];
-                double c = 1.0, s = 0.0, t = 0.0;
-                if (fabs(apq) > tol) {       // Golub & Van Loan, sym.schur2
-                    const double app = L.A[p * LD + p], aqq = L.A[q * LD + q];
-                    const double tau = (aqq - app) / (2.0 * apq);
-                    if (fabs(tau) > 1e150) t = 0.5 / tau;
-                    else t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                    c = 1.0 / sqrt(1.0 + t * t);
-                    s = t * c;
-                    L.rotated = 1;
-                }
-                L.rp[tid] = p; L.rq[tid] = q; L.rc[tid] = c; L.rs[tid] = s; L.rt[tid] = t;
-            }
-            __syncthreads();
-            // A <- J^T A J on the 2x2 blocks (P <= Q, the transpose written too: A stays exactly symmetric)
-            const int nblk = h * (h + 1) / 2;
-            for (int b = tid; b < nblk; b += BLK) {
-                int Pb = 0, rem = b;
-                while (rem >= h - Pb) { rem -= h - Pb; Pb++; }
-                const int Qb = Pb + rem;
-                const int p1 = L.rp[Pb], q1 = L.rq[Pb], p2 = L.rp[Qb], q2 = L.rq[Qb];
-                const double c1 = L.rc[Pb], s1 = L.rs[Pb], c2 = L.rc[Qb], s2 = L.rs[Qb];
-                if (Pb == Qb) {
-                    if (s1 != 0.0) {
-                        const double t1 = L.rt[Pb], apq = L.A[p1 * LD + q1];
-                        L.A[p1 * LD + p1] = L.A[p1 * LD + p1] - t1 * apq;
-                        L.A[q1 * LD + q1] = L.A[q1 * LD + q1] + t1 * apq;
-                        L.A[p1 * LD + q1] = 0.0;
-                        L.A[q1 * LD + p1] = 0.0;
-                    }
-                    continue;
-                }
-                if (s1 == 0.0 && s2 == 0.0) continue;
-                const double b11 = L.A[p1 * LD + p2], b12 = L.A[p1 * LD + q2];
-                const double b21 = L.A[q1 * LD + p2], b22 = L.A[q1 * LD + q2];
-                const double r11 = c1 * b11 - s1 * b21, r12 = c1 * b12 - s1 * b22;     // rows: J_P^T B
-                const double r21 = s1 * b11 + c1 * b21, r22 = s1 * b12 + c1 * b22;
-                const double n11 = c2 * r11 - s2 * r12, n12 = s2 * r11 + c2 * r12;     // columns: (J_P^T B) J_Q
-                const double n21 = c2 * r21 - s2 * r22, n22 = s2 * r21 + c2 * r22;
-                L.A[p1 * LD + p2] = n11; L.A[p1 * LD + q2] = n12; L.A[q1 * LD + p2] = n21; L.A[q1 * LD + q2] = n22;
-                L.A[p2 * LD + p1] = n11; L.A[q2 * LD + p1] = n12; L.A[p2 * LD + q1] = n21; L.A[q2 * LD + q1] = n22;
-            }
-            // V <- V J
-            for (int it = tid; it < M * h; it += BLK) {
-                const int i = it / h, Q = it % h;
-                const double s = L.rs[Q];
-                if (s == 0.0) continue;
-                const double c = L.rc[Q];
-                const int p = L.rp[Q], q = L.rq[Q];
-                const double vp = L.V[i * LD + p], vq = L.V[i * LD + q];
-                L.V[i * LD + p] = c * vp - s * vq;
-                L.V[i * LD + q] = s * vp + c * vq;
-            }
-            __syncthreads();
-        }
-        converged = L.rotated == 0;          // read by every thread after the step's barrier
-        __syncthreads();                     // before thread 0 resets the flag
-    }
+    const bool converged = jacobi_eigh_lds<BLK>(L.A, L.V, Mp, M, LD, jacobi_tol(amax, nrm), L.rc, L.rs, L.rt, L.rp, L.rq, &L.rotated);
     // clip on the diagonal (l[l < eps] = eps), then out = V diag(l) V^T, upper triangle computed and mirrored
     for (int k = tid; k < M; k += BLK) {
         const double l = L.A[k * LD + k];

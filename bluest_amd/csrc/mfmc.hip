@@ -257,13 +257,6 @@ __device__ CliqueEval eval_clique(const Prob &P, uint32_t mask, ScanLds &S, int 
     return E;
 }
 
-__device__ __forceinline__ double wave_min(double x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = fmin(x, __shfl_xor(x, off, WAVE));
-    return x;
-}
-
 __device__ __forceinline__ void atomic_min_pos(double *addr, double v)
 {   // non-negative doubles order like their bit patterns
     atomicMin((unsigned long long *)addr, (unsigned long long)__double_as_longlong(v));

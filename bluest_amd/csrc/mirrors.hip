@@ -1,7 +1,7 @@
 // mirrors.hip -- Part 1 of include/bluest_hip.h: same-name, same-argument-order mirrors of the reference's native module
 // _cmisc_bluest (bluest/cmisc.cpp) on the reference data layout, plus the per-group pseudo-inverse of sap.py:69-79.
 // Pointers may be host or device; host buffers are staged through HBM (compatibility path, PCIe-inclusive).
-#include "common.hpp"
+#include "jacobi.hpp"
 
 // ------------------------------------------------------------------------------------------------------
 // host<->device staging for the "hd" pointers of Part 1
@@ -242,13 +242,11 @@ __global__ __launch_bounds__(64) void k_group_pinv(const double *__restrict__ C,
 // Groups of 17..32 models: two K x K arrays per thread no longer fit the register file, so one wavefront owns one group and
 // keeps the block and its eigenvectors in LDS (two Kp x (Kp + 1) float64 arrays, 16.9 KB at k = 32; Kp = k rounded up to even,
 // the pad index is never coupled and its rotations are identities).  Parallel-ordered cyclic Jacobi (round-robin pairing: Kp/2
-// disjoint rotations per step, Kp - 1 steps per sweep, sweeps until a whole sweep rotates nothing), the 2 x 2 blocks of
-// A <- J^T A J updated together so that A stays exactly symmetric and every annihilated entry exactly zero.  The same cut-off as
-// sym_pinv_jacobi: eigenvalues with |lambda| <= 1e-15 max|lambda| are dropped (numpy.linalg.pinv of the symmetrised block).
-// A group whose sweeps do not converge within WIDE_SWEEPS raises *err (the host turns that into an error, not a result).
+// disjoint rotations per step, Kp - 1 steps per sweep, sweeps until a whole sweep rotates nothing): jacobi_eigh_lds of jacobi.hpp,
+// the eigensolver of covproj.hip's projection with the same numerics.  The same cut-off as sym_pinv_jacobi: eigenvalues with
+// |lambda| <= 1e-15 max|lambda| are dropped (numpy.linalg.pinv of the symmetrised block).
+// A group whose sweeps do not converge within JACOBI_MAX_SWEEPS raises *err (the host turns that into an error, not a result).
 constexpr int WIDE_KMIN = 17;
-constexpr int WIDE_SWEEPS = 40;
-constexpr double WIDE_TOL = 1e-18;        // a rotation is skipped when |a_pq| <= WIDE_TOL * ||A||_F
 
 __host__ __device__ constexpr int wide_kp(int k) { return k + (k & 1); }
 __host__ __device__ constexpr size_t wide_lds_bytes(int k)
@@ -266,7 +264,7 @@ __global__ __launch_bounds__(64) void k_group_pinv_wide(const double *__restrict
     int *rp = reinterpret_cast<int *>(rt + h), *rq = rp + h, *rotated = rq + h;
     const int64_t i = blockIdx.x;
     const G *gi = g + i * k;
-    double nrm = 0.0;
+    double amax = 0.0;
     for (int t = lane; t < Kp * Kp; t += WAVE) {
         const int r = t / Kp, c = t % Kp;
         double a = 0.0;
@@ -276,79 +274,18 @@ __global__ __launch_bounds__(64) void k_group_pinv_wide(const double *__restrict
         }
         A[r * LD + c] = a;
         V[r * LD + c] = (r == c) ? 1.0 : 0.0;
-        nrm += a * a;
+        amax = fmax(amax, fabs(a));
     }
-    nrm = wave_sum(nrm);
-    const double tol = WIDE_TOL * sqrt(nrm);
-    __syncthreads();
-    bool converged = false;
-    for (int sweep = 0; sweep < WIDE_SWEEPS && !converged; sweep++) {
-        if (lane == 0) *rotated = 0;
-        __syncthreads();
-        for (int r = 0; r < Kp - 1; r++) {
-            if (lane < h) {                 // round-robin pairing: (r, Kp-1) and (r+t, r-t) mod (Kp-1)
-                int a, b;
-                if (lane == 0) { a = r; b = Kp - 1; }
-                else           { a = (r + lane) % (Kp - 1); b = (r - lane + (Kp - 1)) % (Kp - 1); }
-                const int p = min(a, b), q = max(a, b);
-                const double apq = A[p * LD + q];
-                double c = 1.0, s = 0.0, t = 0.0;
-                if (fabs(apq) > tol) {
-                    const double app = A[p * LD + p], aqq = A[q * LD + q];
-                    const double tau = (aqq - app) / (2.0 * apq);
-                    if (fabs(tau) > 1e150) t = 0.5 / tau;
-                    else t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                    c = 1.0 / sqrt(1.0 + t * t);
-                    s = t * c;
-                    *rotated = 1;
-                }
-                rp[lane] = p; rq[lane] = q; rc[lane] = c; rs[lane] = s; rt[lane] = t;
-            }
-            __syncthreads();
-            // A <- J^T A J on the 2 x 2 blocks (P <= Q; the transpose written too)
-            const int nblk = h * (h + 1) / 2;
-            for (int b = lane; b < nblk; b += WAVE) {
-                int Pb = 0, rem = b;
-                while (rem >= h - Pb) { rem -= h - Pb; Pb++; }
-                const int Qb = Pb + rem;
-                const int p1 = rp[Pb], q1 = rq[Pb], p2 = rp[Qb], q2 = rq[Qb];
-                const double c1 = rc[Pb], s1 = rs[Pb], c2 = rc[Qb], s2 = rs[Qb];
-                if (Pb == Qb) {
-                    if (s1 != 0.0) {
-                        const double t1 = rt[Pb], apq = A[p1 * LD + q1];
-                        A[p1 * LD + p1] = A[p1 * LD + p1] - t1 * apq;
-                        A[q1 * LD + q1] = A[q1 * LD + q1] + t1 * apq;
-                        A[p1 * LD + q1] = 0.0;
-                        A[q1 * LD + p1] = 0.0;
-                    }
-                    continue;
-                }
-                if (s1 == 0.0 && s2 == 0.0) continue;
-                const double b11 = A[p1 * LD + p2], b12 = A[p1 * LD + q2];
-                const double b21 = A[q1 * LD + p2], b22 = A[q1 * LD + q2];
-                const double r11 = c1 * b11 - s1 * b21, r12 = c1 * b12 - s1 * b22;     // rows: J_P^T B
-                const double r21 = s1 * b11 + c1 * b21, r22 = s1 * b12 + c1 * b22;
-                const double n11 = c2 * r11 - s2 * r12, n12 = s2 * r11 + c2 * r12;     // columns: (J_P^T B) J_Q
-                const double n21 = c2 * r21 - s2 * r22, n22 = s2 * r21 + c2 * r22;
-                A[p1 * LD + p2] = n11; A[p1 * LD + q2] = n12; A[q1 * LD + p2] = n21; A[q1 * LD + q2] = n22;
-                A[p2 * LD + p1] = n11; A[q2 * LD + p1] = n12; A[p2 * LD + q1] = n21; A[q2 * LD + q1] = n22;
-            }
-            // V <- V J (rows of the pad index stay e_pad: the pad is never rotated)
-            for (int it = lane; it < k * h; it += WAVE) {
-                const int r2 = it / h, Q = it % h;
-                const double s = rs[Q];
-                if (s == 0.0) continue;
-                const double c = rc[Q];
-                const int p = rp[Q], q = rq[Q];
-                const double vp = V[r2 * LD + p], vq = V[r2 * LD + q];
-                V[r2 * LD + p] = c * vp - s * vq;
-                V[r2 * LD + q] = s * vp + c * vq;
-            }
-            __syncthreads();
+    amax = wave_max(amax);
+    double nrm = 0.0;                         // sum (a / max|a|)^2 (each lane rereads its own entries): see jacobi_tol
+    if (amax > 0.0)
+        for (int t = lane; t < Kp * Kp; t += WAVE) {
+            const double a = A[(t / Kp) * LD + t % Kp] / amax;
+            nrm += a * a;
         }
-        converged = *rotated == 0;
-        __syncthreads();                    // before lane 0 resets the flag
-    }
+    nrm = wave_sum(nrm);
+    __syncthreads();
+    const bool converged = jacobi_eigh_lds<WAVE>(A, V, Kp, k, LD, jacobi_tol(amax, nrm), rc, rs, rt, rp, rq, rotated);
     if (!converged) {
         if (lane == 0) atomicOr(err, 1);
         return;
@@ -517,7 +454,7 @@ static int launch_group_pinv_wide(const double *dC, int N, int k, int64_t Lk, co
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&h_err, ew.word, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (h_err) return fail(BLUEST_ERR_STATE, "group pseudo-inverse (k=%d): Jacobi sweeps did not converge within %d sweeps", k, WIDE_SWEEPS);
+    if (h_err) return fail(BLUEST_ERR_STATE, "group pseudo-inverse (k=%d): Jacobi sweeps did not converge within %d sweeps", k, JACOBI_MAX_SWEEPS);
     return BLUEST_OK;
 }
 

@@ -9,7 +9,7 @@
 // The algorithm is restated in numpy by the test infrastructure; tests compare the two.
 // The reference hands this problem to third-party NLP solvers with the Hessian of bluest/misc.py:497-503 /
 // bluest/cmisc.cpp:74-97 (bluest/sap.py:387-456); there is no reference code to follow.
-#include "plan.hpp"     // brings solve.hpp: readlane_f64, wave_lds_sync
+#include "plan.hpp"     // brings solve.hpp: readlane_f64, dpp_f64
 
 #define MASTER_THREADS 512
 #define MASTER_SMAX 64
@@ -275,16 +275,6 @@ __device__ __forceinline__ void row16_pick(double &best, int &who)
     row16_pick_step<MAXI, 0x140>(best, who);
 }
 
-// x of the lane whose index within its quad differs in bit 0 (CTRL 0xB1 = quad_perm:[1,0,3,2]) or bit 1 (0x4E = quad_perm:[2,3,0,1]):
-// a DPP move per 32-bit half, no LDS crossbar (ds_bpermute) involved
-template <int CTRL>
-__device__ __forceinline__ double quad_xor(double x)
-{
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
 // forward elimination beyond 32 models (no DPP: a DPP row has 16 lanes), rows in registers, only what the LAST pivot needs: the
 // elimination of solve.hpp's gj_regs as a template recursion with the broadcasts in chunks of 16 (a[NT] and NT broadcasts at once
 // do not fit the 256 registers a wavefront of this 512-thread kernel has)
@@ -412,18 +402,20 @@ __device__ void master_eval(const MasterArgs &A, MasterLds &L, const double *xv,
                 for (int q = 0; q < 8; q++) if (o0 + q < n_out) acc[q] = fma(mj, B[(size_t)(o0 + q) * KE], acc[q]);
             }
             // the quad's partial sums of up to eight outputs -> lane `sub` ends with the totals of outputs o0 + 2 sub, + 1: a transposing
-            // butterfly (4 + 2 exchanges; every lane folds the half it keeps and hands over the other), DPP quad permutes, fixed order
+            // butterfly (4 + 2 exchanges; every lane folds the half it keeps and hands over the other), DPP quad permutes, fixed order.
+            // dpp_f64<CTRL>(x) is x of the lane whose index within its quad differs in bit 1 (CTRL 0x4E = quad_perm:[2,3,0,1]) or bit 0
+            // (0xB1 = quad_perm:[1,0,3,2]): a DPP move per 32-bit half, no LDS crossbar (ds_bpermute) involved
             const bool h2 = (sub & 2) != 0, h1 = (sub & 1) != 0;
             double k4[4], k2[2];
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const double give = h2 ? acc[i] : acc[4 + i], keep = h2 ? acc[4 + i] : acc[i];
-                k4[i] = keep + quad_xor<0x4E>(give);
+                k4[i] = keep + dpp_f64<0x4E>(give);
             }
 #pragma unroll
             for (int i = 0; i < 2; i++) {
                 const double give = h1 ? k4[i] : k4[2 + i], keep = h1 ? k4[2 + i] : k4[i];
-                k2[i] = keep + quad_xor<0xB1>(give);
+                k2[i] = keep + dpp_f64<0xB1>(give);
             }
             if (st0) { const double v = k2[0] + base0; P0[ia] = v; P0[ib] = v; }
             if (st1) { const double v = k2[1] + base1; P1[ia] = v; P1[ib] = v; }

@@ -156,15 +156,6 @@ __device__ __forceinline__ void fold_rows(SolveLds<NT> &lds, int N, const RowDes
     }
 }
 
-// single-wavefront LDS ordering: LDS operations of one wave execute in order; this only stops the compiler from
-// moving LDS accesses across it and drains lgkmcnt
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 __device__ __forceinline__ int uniform_i(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
 __device__ __forceinline__ double rcp_f64(double x)

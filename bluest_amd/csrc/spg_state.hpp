@@ -40,14 +40,6 @@
 #define SPG_STATE_DOUBLES 256
 #define SPG_MAX_OUT  64
 
-
-__device__ __forceinline__ void spg_wave_lds_sync()
-{   // one wavefront: its LDS operations execute in order; keep the compiler from moving them and drain the counter
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 // objective of the trial from the per-output variances, nonmonotone Armijo test, safeguarded quadratic interpolation
 // (bluest/spg.py:9-35).  ONE wavefront (lane = 0..63): the state is staged through `ls` (SPG_STATE_DOUBLES doubles of LDS) with
 // coalesced loads, lane o handles output o, lane 0 takes the decision.  On the last slot of an iteration it also sets the
@@ -86,7 +78,7 @@ __device__ __forceinline__ void spg_decide_wave(double *__restrict__ st, const d
 {   // own: single-output plan, lane 0 passes V and status of its own solve in registers (nothing is read back from memory)
 #pragma unroll
     for (int t = 0; t < SPG_STATE_DOUBLES / 64; t++) ls[t * 64 + lane] = pf.w[t];
-    spg_wave_lds_sync();
+    wave_lds_sync();
     const bool idle = ls[SPG_DONE] != 0.0 || ls[SPG_FAIL] != 0.0;
     if (idle || ls[SPG_ACCEPT] != 0.0) {
         if (last_slot && lane == 0) *enable = (!idle && ls[SPG_ACCEPT] != 0.0) ? 1 : 0;

@@ -233,7 +233,7 @@ def reference(name):
     raise KeyError(name)
 
 
-# ---- the recorded runs of the reference project (tests/golden/covproj_*.npz) -------------------------------------------
+# ---- the recorded runs of the reference project (tests/golden/covproj_*_M*.npz) -------------------------------------------
 # The recorded run of this input (one matrix, two fixtures) takes 225 iterations, the restatement 221: at iteration 88 an
 # Armijo test is decided by 7.6e-8 where rounding in the projections can move it by 1.4e-7, and 20 more tests like it follow.
 # Such a run is not determined by its input in float64; these two are judged on err (and cov) alone.
@@ -249,3 +249,29 @@ def fixture_inputs(g, n):
     np.fill_diagonal(mask, 1.0)
     params = {"maxit": int(g["maxit"])} if int(g["maxit"]) >= 0 else {}
     return np.where(mask > 0, C, 0.0), mask, params
+
+
+# ---- the rows whose results are held bit for bit (tests/golden/covproj_bits_parent.npz, test_gpu_covproj_bits.py) --------
+# The smallest that reach each part of the shared eigensolver: one pair and one step per sweep (M = 2); an odd size, so the
+# pad index is live (M = 3); M = 4, plain and with entries whose squares overflow; 16 rotations per step with and without
+# the pad (M = 31, 32); more 2 x 2 blocks per step (528) than the workgroup has threads (M = 64); and three SPG iterations,
+# so that projections chain.
+BITS_FIELDS = ("X", "f", "gpmax", "it", "count", "info")
+
+
+@functools.lru_cache(maxsize=None)
+def bits_cases():
+    return (case("clip_indefinite_M2"), case("clip_indefinite_M3"),
+            _row("clip_indefinite_M4", "clip", indefinite(4, 4000), np.ones((4, 4)), spd_threshold=5.0e-14), overflow_case(),
+            case("clip_indefinite_M31"), case("clip_clustered_M32"), case("clip_indefinite_M64"),
+            dict(case("spg_40pc_M13_h10"), name="spg_40pc_M13_h10_maxit3", params={"maxit": 3}))
+
+
+BITS_NAMES = tuple(r["name"] for r in bits_cases())
+
+
+def bits_record(solo, row):
+    """what the record holds of one row: the six outputs of one call (`solo(row)`: one launch, one output), keyed <name>/<field>"""
+    X, f, gpmax, it, count, info = solo(row)
+    vals = (X, np.float64(f), np.float64(gpmax), np.int64(it), np.int64(count), np.int32(info))
+    return {"%s/%s" % (row["name"], k): np.asarray(v) for k, v in zip(BITS_FIELDS, vals)}

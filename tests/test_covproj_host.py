@@ -8,7 +8,7 @@ import pytest
 
 from conftest import GOLDEN, golden
 
-CASES = sorted(os.path.basename(p)[len("covproj_"):-len(".npz")] for p in glob.glob(os.path.join(GOLDEN, "covproj_*.npz")))
+CASES = sorted(os.path.basename(p)[len("covproj_"):-len(".npz")] for p in glob.glob(os.path.join(GOLDEN, "covproj_*_M*.npz")))
 
 
 def test_cov_project_declared_and_bound():

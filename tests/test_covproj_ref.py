@@ -1,6 +1,6 @@
 """
 CPU tests of oracle/covproj_ref.py, the numpy restatement of bluest_cov_project that test_gpu_covproj_abi.py compares the
-kernel with: the restatement reproduces the recorded runs of the reference project (tests/golden/covproj_*.npz, `it` and
+kernel with: the restatement reproduces the recorded runs of the reference project (tests/golden/covproj_*_M*.npz, `it` and
 `count` included), every decision it takes on every row of tests/covproj_cases.py is further from flipping than float64
 rounding in the kernel can move it, and the table reaches every path of the kernel that an input can reach.
 """
@@ -14,7 +14,7 @@ import covproj_cases as cc
 from conftest import GOLDEN, golden
 from oracle import covproj_ref as ref
 
-FIXTURES = sorted(os.path.basename(p)[len("covproj_"):-len(".npz")] for p in glob.glob(os.path.join(GOLDEN, "covproj_*.npz")))
+FIXTURES = sorted(os.path.basename(p)[len("covproj_"):-len(".npz")] for p in glob.glob(os.path.join(GOLDEN, "covproj_*_M*.npz")))
 MARGINAL, fixture_inputs = cc.FIXTURE_MARGINAL, cc.fixture_inputs
 
 

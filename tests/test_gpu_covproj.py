@@ -14,7 +14,7 @@ from conftest import GOLDEN, golden
 
 pytestmark = pytest.mark.gpu
 
-CASES = sorted(os.path.basename(p)[len("covproj_"):-len(".npz")] for p in glob.glob(os.path.join(GOLDEN, "covproj_*.npz")))
+CASES = sorted(os.path.basename(p)[len("covproj_"):-len(".npz")] for p in glob.glob(os.path.join(GOLDEN, "covproj_*_M*.npz")))
 THR = 5.0e-14
 
 

@@ -93,6 +93,37 @@ def test_group_pinv_wide_vs_numpy(gpu, oracle, k):
             assert np.linalg.norm(ref_c[i] - want) / np.linalg.norm(want) <= max(tol, 1e-12), (k, kind, "oracle")
 
 
+def test_group_pinv_wide_scaled_norm(gpu):
+    """pinv(2^515 C) == 2^-515 pinv(C), bit for bit, on both paths (int64 groups of bluest_group_pinv, uint8 groups of the plan's
+    set-up).  The entries of 2^515 C are near 1e155: a plain sum of their squares is inf, and with it the rotation tolerance, so
+    no rotation would be taken and diag(1 / a_ii) returned as a converged result; the norm is formed from entries scaled by the
+    largest.  Every operation of the routine commutes with a power-of-two scale (the rotation angles come from the scale-free
+    tau, the cut-off is relative, nothing underflows or overflows at these magnitudes), hence equality rather than a tolerance."""
+    from bluest_amd import misc
+    from bluest_amd.plan import Plan
+    n = 32
+    C, rng = _wishart(n, 515)
+    scale = 2.0 ** 515
+    with np.errstate(over="ignore"):
+        assert np.isinf(((scale * C[:17, :17]) ** 2).sum()) and np.isfinite(scale * C).all()
+    for k, gl in ((17, [np.sort(rng.choice(n, 17, replace=False)) for _ in range(2)]), (32, [np.arange(32), np.arange(32)])):
+        g = np.ascontiguousarray(np.array(gl, dtype=np.int64))
+        sizes = [0] * (k - 1) + [len(gl)]
+
+        def both(Cx):
+            plan = Plan(n, len(gl), [{"K": k, "sizes": sizes, "groups": [np.zeros((0, j), dtype=np.int64) for j in range(1, k)] + [g],
+                                      "C": Cx, "mapping": None}])
+            return (misc.group_pinv(Cx, k, g).reshape(len(gl), k, k), np.asarray(plan.invcovs[0]).reshape(len(gl), k, k).copy())
+        for path, small, big in zip(("int64", "uint8"), both(C), both(scale * C)):
+            want = small / scale                                  # exact: a power of two, far from the subnormals
+            assert np.isfinite(big).all() and np.abs(want).min() > 1e-200, (k, path)
+            for i, gi in enumerate(gl):                           # the unscaled side is a pseudo-inverse at all
+                ref = _pinv_ref(C, gi)
+                assert np.linalg.norm(small[i] - ref) / np.linalg.norm(ref) <= 1e-12, (k, path, i)
+            print("k=%d %s: %d of %d entries differ" % (k, path, int((big != want).sum()), big.size))
+            assert np.array_equal(big, want), (k, path)
+
+
 def test_group_size_limit_is_enforced(gpu):
     """33 models in one group: refused with BLUEST_ERR_ARG and a message naming the limit (plan and mirror alike)"""
     from bluest_amd import misc
