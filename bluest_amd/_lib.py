@@ -90,6 +90,7 @@ SIGNATURES = {
     "bluest_simplex_workspace_doubles": [c_i64, c_i64p],
     "bluest_simplex_project": [c_vp, c_vp, c_f64, c_f64, c_f64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
     "bluest_mfmc_search": [c_int, c_int, c_int, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "bluest_mlmc_search": [c_int, c_int, c_int, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "bluest_cov_project": [c_int, c_int, c_vp, c_vp, c_f64, c_f64, c_f64, c_f64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                            c_vp, c_vp],
 }

@@ -9,7 +9,7 @@ The projection of the covariances onto the SPD matrices (`project_covariance(s)`
 the eigendecompositions and the whole SPG solve run on the GPU (bluest_cov_project, one workgroup per output).  The
 constructor runs it only when asked (`skip_projection=False`; the default here is True, the reference's is False).
 Out of scope (refused with BLUESTError): estimating covariances or costs by sampling, saving /
-loading model graphs, the MLMC driver.  MFMC (setup_mfmc / solve_mfmc / compute_mfmc_data, the subset search on the
+loading model graphs, and -- on this class alone -- the MLMC driver (bluest_amd.mlmc.MLMCMixin provides it).  MFMC (setup_mfmc / solve_mfmc / compute_mfmc_data, the subset search on the
 GPU) and plain Monte Carlo (solve_mc) are in scope.  An MPI communicator passed
 as `comm` is honoured the way the reference uses it (optimiser, estimators and projection on rank 0 + bcast, samples split
 over the ranks).
@@ -178,6 +178,11 @@ class BLUEProblem(object):
         Cs = list(C) if isinstance(C, (list, tuple)) else [C]
         if len(Cs) != self.n_outputs or any(np.shape(c) != (self.M, self.M) for c in Cs):
             raise ValueError("need one %d x %d covariance per output" % (self.M, self.M))
+        if mlmc_variances is None:                             # bluest/blue_models.py:77-92
+            dV = [np.nan * np.ones((self.M, self.M)) for n in range(self.n_outputs)]
+        else:
+            dV = mlmc_variances
+        self.dV = dV if isinstance(dV, (list, tuple)) else [dV]
         self._costs = np.array(costs, dtype=np.float64)
         if self._costs.shape != (self.M,):
             raise ValueError("costs must have one entry per model")
@@ -230,6 +235,12 @@ class BLUEProblem(object):
 
     def get_covariances(self):
         return [cp.covariance() for cp in self._coupling]
+
+    def get_mlmc_variances(self):
+        return self.dV
+
+    def get_mlmc_variance(self, n=0):
+        return self.dV[n]
 
     def get_correlation(self, n=0):
         C = self.get_covariance(n)

@@ -13,13 +13,16 @@
 //
 // Arithmetic follows the reference expression by expression (float64, no contraction) so that feasibility and rounding decide
 // the same way.
-#include "common.hpp"
+#include "subset_search.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int BLK = 256;
+using subset_search::BLK;
+using subset_search::CAND_CAP;
+using subset_search::atomic_min_pos;
+using subset_search::atomic_max_pos;
 constexpr int MAXL = BLUEST_MFMC_MAX_NEIGHBOURS + 1;      // models in a clique, model 0 included
 // Relative slack of the lower bound.  The reference's variance sum s0^2/m0 + sum (1/m_{i-1} - 1/m_i) c_i cancels down to at least
 // s0^2 (1 - rho_1^2)/m0, and its terms are at most ~3 s0^2/m0 in size.  Its rounding error relative to the result is therefore
@@ -27,16 +30,6 @@ constexpr int MAXL = BLUEST_MFMC_MAX_NEIGHBOURS + 1;      // models in a clique,
 // optimum by at most that much, so the lower bound is taken that much lower (never below 1e-9, never below zero).
 constexpr double LB_MARGIN_MIN = 1e-9;
 constexpr double LB_MARGIN_ULPS = 16.0;
-constexpr int64_t CAND_CAP = 1 << 16;                      // cliques rounded per window
-// Counting scans the window loop may spend between two windows that round a clique.  A window that rounds something consumes
-// cliques, and there are at most 2^30; a window that comes out empty (the halving overshot below the next lower bound v) at
-// least halves the distance from lo to v, and the next one needs one more halving to get there.  From hi - lo down to the
-// spacing of doubles at v that is E <= log2((hi - lo) / v) + 53 empty windows of 1, 2, ..., E halvings, E^2/2 scans in all.
-// Lower and upper bounds of one problem are sample costs or errors of the same models: a range of 2^30 between them gives
-// E <= 83 and fewer than 3500 scans.  Only lower bounds of exactly zero (|rho_1| = 1: more than CAND_CAP cliques at LB = 0,
-// lo = -1 halving towards them for 1074 windows, some 5e5 scans) need more, and they end in the same message either way.
-constexpr int MAX_IDLE_SCANS = 4096;
-
 struct Prob {
     int nb, n_out, budget_mode, continuous, small_budget, integer_round;
     double budget;
@@ -61,17 +54,19 @@ __device__ __forceinline__ bool is_clique(const Prob &P, uint32_t mask)
 }
 
 // enumeration order of networkx.enumerate_all_cliques for cliques through model 0: size, then lexicographic
-__device__ __forceinline__ bool earlier(uint32_t a, uint32_t b)
-{
-    const int pa = __popc(a), pb = __popc(b);
-    if (pa != pb) return pa < pb;
-    const uint32_t d = a ^ b;
-    return d != 0u && ((a & (d & (0u - d))) != 0u);
-}
+struct CliqueOrder {
+    static __device__ __forceinline__ bool before(uint32_t a, uint32_t b)
+    {
+        const int pa = __popc(a), pb = __popc(b);
+        if (pa != pb) return pa < pb;
+        const uint32_t d = a ^ b;
+        return d != 0u && ((a & (d & (0u - d))) != 0u);
+    }
+};
 
 __device__ __forceinline__ bool better(double fa, uint32_t ma, double fb, uint32_t mb)
 {
-    return fa < fb || (fa == fb && fa < INFINITY && earlier(ma, mb));
+    return subset_search::better<CliqueOrder>(fa, ma, fb, mb);
 }
 
 // one output of one clique: its models in |rho| order (per-thread column of LDS)
@@ -257,31 +252,6 @@ __device__ CliqueEval eval_clique(const Prob &P, uint32_t mask, ScanLds &S, int 
     return E;
 }
 
-__device__ __forceinline__ void atomic_min_pos(double *addr, double v)
-{   // non-negative doubles order like their bit patterns
-    atomicMin((unsigned long long *)addr, (unsigned long long)__double_as_longlong(v));
-}
-__device__ __forceinline__ void atomic_max_pos(double *addr, double v)
-{
-    atomicMax((unsigned long long *)addr, (unsigned long long)__double_as_longlong(v));
-}
-
-// block-wide argmin of (f, mask) under better(); result valid in thread 0
-__device__ void block_best(double &f, uint32_t &m, double *redf, uint32_t *redm, int tid)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        const double of = __shfl_xor(f, off, WAVE);
-        const uint32_t om = __shfl_xor(m, off, WAVE);
-        if (better(of, om, f, m)) { f = of; m = om; }
-    }
-    if ((tid & 63) == 0) { redf[tid >> 6] = f; redm[tid >> 6] = m; }
-    __syncthreads();
-    if (tid == 0)
-        for (int k = 1; k < (int)(blockDim.x >> 6); k++)
-            if (better(redf[k], redm[k], f, m)) { f = redf[k]; m = redm[k]; }
-    __syncthreads();
-}
-
 // pass 0 (exact modes): per-block best clique.  pass 1 (integer): min UB, max finite LB, the > 24 flag.
 // pass 2 (integer): count cliques with lo < LB <= hi.  pass 3: collect them (first CAND_CAP).
 __global__ __launch_bounds__(BLK) void k_mfmc_scan(Prob P, int pass, uint64_t total, double lo, double hi, double *partf,
@@ -307,7 +277,7 @@ __global__ __launch_bounds__(BLK) void k_mfmc_scan(Prob P, int pass, uint64_t to
         }
     }
     if (pass == 0) {
-        block_best(bf, bm, S.redf, S.redm, tid);
+        subset_search::block_best<CliqueOrder>(bf, bm, S.redf, S.redm, tid);
         if (tid == 0) { partf[blockIdx.x] = bf; partm[blockIdx.x] = bm; }
     } else if (pass == 1) {
         ub = wave_min(ub);
@@ -432,40 +402,7 @@ __global__ __launch_bounds__(BLK) void k_mfmc_round(Prob P, const uint32_t *cand
     }
 }
 
-// best of `count` (obj, mask[, combos]) records merged into best[0] (obj) / bmask[0] / bcombo[n_out]
-__global__ __launch_bounds__(BLK) void k_mfmc_pick(int64_t count, const double *f, const uint32_t *m, const uint32_t *idxmask,
-                                                   const uint32_t *combo, int n_out, double *best, uint32_t *bmask,
-                                                   uint32_t *bcombo)
-{
-    __shared__ double redf[BLK / WAVE];
-    __shared__ uint32_t redm[BLK / WAVE];
-    __shared__ int64_t redk[BLK / WAVE];
-    const int tid = threadIdx.x;
-    double bf = INFINITY;
-    uint32_t bm = 0xffffffffu;
-    int64_t bk = -1;
-    for (int64_t k = tid; k < count; k += BLK) {
-        const uint32_t mk = idxmask ? idxmask[k] : m[k];
-        if (better(f[k], mk, bf, bm)) { bf = f[k]; bm = mk; bk = k; }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double of = __shfl_xor(bf, off, WAVE);
-        const uint32_t om = __shfl_xor(bm, off, WAVE);
-        const int64_t ok = __shfl_xor(bk, off, WAVE);
-        if (better(of, om, bf, bm)) { bf = of; bm = om; bk = ok; }
-    }
-    if ((tid & 63) == 0) { redf[tid >> 6] = bf; redm[tid >> 6] = bm; redk[tid >> 6] = bk; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int k = 1; k < BLK / WAVE; k++)
-            if (better(redf[k], redm[k], bf, bm)) { bf = redf[k]; bm = redm[k]; bk = redk[k]; }
-        if (bk >= 0 && better(bf, bm, best[0], bmask[0])) {
-            best[0] = bf;
-            bmask[0] = bm;
-            if (combo) for (int n = 0; n < n_out; n++) bcombo[n] = combo[bk * n_out + n];
-        }
-    }
-}
+constexpr auto k_mfmc_pick = subset_search::k_pick<CliqueOrder>;
 
 }  // namespace
 
@@ -546,49 +483,26 @@ extern "C" int bluest_mfmc_search(int nb, int n_out, int flags, double budget, c
         HIP_TRY(hipMemcpyAsync(hs, stats, 24, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (hs[2] > 0.0) { *status = BLUEST_MFMC_TOO_BIG; return BLUEST_OK; }
-        const double U = hs[0], LBmax = hs[1];
-        double lo = -1.0, best = INFINITY;
-        int idle = 0;                                   // counting scans since a window last rounded a clique
-        auto count_in = [&](int pass, double a, double b, unsigned long long *out) -> int {
-            if (pass == 2) idle++;
+        auto count_in = [&](bool collect, double a, double b, unsigned long long *out) -> int {
             HIP_TRY(hipMemsetAsync(cnt, 0, 8, st));
-            hipLaunchKernelGGL(k_mfmc_scan, dim3(grid), dim3(BLK), 0, st, P, pass, total, a, b, partf, partm, stats, cnt, cand);
+            hipLaunchKernelGGL(k_mfmc_scan, dim3(grid), dim3(BLK), 0, st, P, collect ? 3 : 2, total, a, b, partf, partm, stats, cnt,
+                               cand);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(out, cnt, 8, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             return BLUEST_OK;
         };
-        while (true) {                                  // windows lo < LB <= T of increasing LB, at most CAND_CAP cliques each
-            const double hi = std::min(std::min(U, best), LBmax);
-            if (!(lo < hi)) break;
-            double T = hi;
-            unsigned long long c = 0;
-            if ((rc = count_in(2, lo, T, &c))) return rc;
-            for (int it = 0; c > (unsigned long long)CAND_CAP; it++) {
-                if (it >= 200) return fail(BLUEST_ERR_STATE, "more than %lld cliques share one lower bound", (long long)CAND_CAP);
-                T = lo + 0.5 * (T - lo);
-                if (!(T > lo)) break;
-                if ((rc = count_in(2, lo, T, &c))) return rc;
-            }
-            if (!(T > lo) || c > (unsigned long long)CAND_CAP)     // the window cannot advance: never loop on it
-                return fail(BLUEST_ERR_STATE, "more than %lld cliques share one lower bound", (long long)CAND_CAP);
-            if (idle >= MAX_IDLE_SCANS)                             // checked once per window, halvings included
-                return fail(BLUEST_ERR_STATE, "%d counting scans without a clique to round: the lower bounds cluster too "
-                            "closely for windows of %lld (more than that many share one lower bound)", idle, (long long)CAND_CAP);
-            if (c > 0) {
-                if ((rc = count_in(3, lo, T, &c))) return rc;
-                c = std::min(c, (unsigned long long)CAND_CAP);
-                hipLaunchKernelGGL(k_mfmc_round, dim3((unsigned)c), dim3(BLK), 0, st, P, (const uint32_t *)cand, cobj, cc);
-                HIP_TRY(hipGetLastError());
-                hipLaunchKernelGGL(k_mfmc_pick, dim3(1), dim3(BLK), 0, st, (int64_t)c, (const double *)cobj,
-                                   (const uint32_t *)nullptr, (const uint32_t *)cand, (const uint32_t *)cc, n_out, bf, bm, bc);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(&best, bf, 8, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                idle = 0;
-            }
-            lo = T;
-        }
+        auto round_them = [&](unsigned long long c, double *best) -> int {
+            hipLaunchKernelGGL(k_mfmc_round, dim3((unsigned)c), dim3(BLK), 0, st, P, (const uint32_t *)cand, cobj, cc);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_mfmc_pick, dim3(1), dim3(BLK), 0, st, (int64_t)c, (const double *)cobj,
+                               (const uint32_t *)nullptr, (const uint32_t *)cand, (const uint32_t *)cc, n_out, bf, bm, bc);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(best, bf, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            return BLUEST_OK;
+        };
+        if ((rc = subset_search::window_loop(hs[0], hs[1], "clique", count_in, round_them))) return rc;
     }
     HIP_TRY(hipMemcpyAsync(best_obj, bf, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(best_mask, bm, 4, hipMemcpyDeviceToHost, st));

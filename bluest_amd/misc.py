@@ -250,3 +250,56 @@ def compute_mfmc_data(sigmas, rhos, costs, samples):
     m = np.array(samples)[idx]
     variance = _mfmc_variance(s, rho, alphas)(m)
     return True, {"samples": m, "error": np.sqrt(variance), "total_cost": m @ w, "alphas": alphas, "variance": variance}
+
+
+# ---- MLMC (bluest/misc.py:15-46; bluest/blue_models.py:689-704): numpy mirrors for ONE model group ---------------------
+# O(L) each (the brute-force rounding O(2^L)); the search over groups is bluest_mlmc_search (csrc/mlmc.hip).
+
+def mlmc_levels(C, dV, w, group):
+    """blue_models.py:689-704: (v, c), the level variances and level costs of `group` (model 0 first, by decreasing cost).
+    Level i couples group[i] with group[i+1]; dV[min, max] replaces its variance where finite; the last level is the last
+    model alone"""
+    group = [int(g) for g in group]
+    subC = np.asarray(C, dtype=np.float64)[np.ix_(group, group)]
+    subw = np.asarray(w, dtype=np.float64)[group].copy()
+    if len(group) > 1:
+        v, corrs = np.diag(subC).copy(), np.diag(subC, 1)
+        v[:-1] += v[1:] - 2 * corrs
+        for i in range(len(group) - 1):
+            check = dV[min(group[i], group[i + 1]), max(group[i], group[i + 1])]
+            if np.isfinite(check):
+                v[i] = check
+        subw[:-1] += subw[1:]
+    else:
+        v = subC[0].copy()
+    return v, subw
+
+
+def mlmc_allocation(v, w, budget=None, eps=None):
+    """misc.py:23-29: (continuous allocation >= 1, variance callable)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = sum(np.sqrt(v * w))
+        mu = budget / q if budget is not None else q / eps**2
+        m = np.maximum(mu * np.sqrt(v / w), 1)
+    return m, lambda m: sum(v[m > 0] / m[m > 0])
+
+
+def attempt_mlmc_setup(v, w, budget=None, eps=None, continuous_relaxation=False):
+    """misc.py:15-46: (feasible, {"samples", "error", "total_cost", "variance"}) for level variances v and level costs w"""
+    if budget is None and eps is None:
+        raise ValueError("Need to specify either budget or RMSE tolerance")
+    elif budget is not None and eps is not None:
+        eps = None
+    v, w = np.asarray(v, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    if not all(np.isfinite(v)): return False, None
+    m, variance = mlmc_allocation(v, w, budget=budget, eps=eps)
+    if budget is not None:
+        constraint = lambda m: m @ w <= budget and all(m >= 1)
+        obj = variance
+    else:
+        constraint = lambda m: variance(m) <= eps**2 and all(m >= 1)
+        obj = lambda m: m @ w
+    if not continuous_relaxation:
+        m, fval = _best_closest_integer_solution(m, obj, constraint)
+        if np.isinf(fval): return False, None
+    return True, {"samples": m, "error": np.sqrt(variance(m)), "total_cost": m @ w, "variance": variance}

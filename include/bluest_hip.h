@@ -470,6 +470,37 @@ int bluest_cov_project(int M, int n_out, const double *C, const double *mask, do
                        double lmbda_max, int64_t maxit, int64_t max_fevals, int hlength, double *X_out, double *f_out,
                        double *gpmax_out, int64_t *it_out, int64_t *count_out, int32_t *info_out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Part 9 -- MLMC model-subset search (bluest/blue_models.py:642-741; allocation misc.py:15-46, rounding misc.py:141-167,
+ * 384-413).  Positions 0..nb are the models in decreasing cost order, model 0 at position 0 (the host orders them and drops
+ * the models dearer than model 0).  Host arrays: w (nb+1) model costs by position; lv (n_out x (nb+1) x (nb+1)) level variances:
+ * lv[n][p][q], p < q, the variance of the difference of the models at p and q (C[p,p] + (C[q,q] - 2 C[p,q]), or the user's
+ * mlmc_variances entry where finite), lv[n][p][p] = C[p,p] the last level of a group ending at p, q < p unused; eps2 (n_out)
+ * eps**2 (eps mode only); adj (nb+1) bit q set when positions p and q are coupled in the intersection of the coupling graphs.
+ * A group is a bitmask over positions 1..nb (bit p-1 = position p kept): position 0, then the kept positions in increasing
+ * order, admissible when every consecutive pair is coupled (a path, not a clique; mask 0 always is).  Its levels are
+ * (g_i, g_i+1) with cost w[g_i] + w[g_i+1], and g_L-1 alone.  Searches all 2^nb masks and returns the reference's argmin of
+ *   budget mode: the largest error over outputs;
+ *   eps mode:    sum_i (max over outputs of the samples of level i) * w[g_i] -- the MODEL costs, not the level costs: the
+ *                reference's choice (blue_models.py:718), kept;
+ * ties going to the reference's enumeration order (mask 0, then by decreasing size, then the removed positions in lexicographic
+ * order): best_mask, best_combo (n_out: the index of the floor/ceil combination the rounding chose, bit j = ub of the j-th
+ * entry of get_feasible_integer_bounds; 0 in continuous mode), best_obj, status.  On BLUEST_MLMC_TOO_BIG only status is
+ * written.  nb outside 0..BLUEST_MLMC_MAX_CANDIDATES, n_out outside 1..BLUEST_MLMC_MAX_OUTPUTS, a null pointer, or eps mode
+ * without eps2 return BLUEST_ERR_ARG.  Synchronous on `stream`; allocates and frees its own device memory.
+ * --------------------------------------------------------------------------------------------------------- */
+#define BLUEST_MLMC_MAX_CANDIDATES 30   /* models below model 0 in cost order */
+#define BLUEST_MLMC_MAX_ROUND      24   /* 'Too many dimensions to brute-force it' above this group size */
+#define BLUEST_MLMC_MAX_OUTPUTS    64
+#define BLUEST_MLMC_BUDGET         1    /* flags */
+#define BLUEST_MLMC_CONTINUOUS     2
+#define BLUEST_MLMC_OK             0    /* status */
+#define BLUEST_MLMC_NONE           1    /* no group admits an MLMC estimator */
+#define BLUEST_MLMC_TOO_BIG        2    /* an admissible group with finite level variances has more than BLUEST_MLMC_MAX_ROUND models */
+int bluest_mlmc_search(int nb, int n_out, int flags, double budget, const double *eps2, const double *w, const double *lv,
+                       const uint32_t *adj, uint32_t *best_mask, uint32_t *best_combo, double *best_obj, int32_t *status,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
