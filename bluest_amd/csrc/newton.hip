@@ -1654,6 +1654,7 @@ extern "C" int bluest_price_capped(bluest_plan_t plan, const double *grad_dev, c
     if (capmask_dev && (!nu_dev || !master_out_dev)) return fail(BLUEST_ERR_ARG, "null pointer");
     if (!plan || !grad_dev || !mu_dev || !s_dev || !cc_dev || !sup_dev || !c_sup_dev || !top_val_dev || !top_idx_dev || !y0_dev) return fail(BLUEST_ERR_ARG, "null pointer");
     if (!plan->finalized) return fail(BLUEST_ERR_STATE, "plan not finalized");
+    if (S <= 0) return fail(BLUEST_ERR_ARG, "sizes out of range");
     const int n_out = (int)plan->outs.size();
     hipLaunchKernelGGL(k_price, dim3(PRICE_BLOCKS), dim3(256), 0, (hipStream_t)stream, plan->L, n_out, grad_dev, plan->d_goff,
                        plan->identity ? nullptr : plan->d_invmap, mu_dev, s_dev, cc_dev, S, sup_dev, c_sup_dev, top_val_dev, top_idx_dev, plan->d_v, plan->N, y0_dev,
