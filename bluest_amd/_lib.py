@@ -84,6 +84,7 @@ SIGNATURES = {
     "bluest_plan_launch_config": [c_vp, c_int, c_vp],
     "bluest_launch_set": [c_int, c_vp, c_int, ctypes.POINTER(c_int)],
     "bluest_wave_reduce_probe": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "bluest_wave_reduce_multi_probe": [c_vp, c_i64, c_int, c_vp, c_vp],
     "bluest_support_point": [c_i64, c_int, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp],
     "bluest_price": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "bluest_price_capped": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],

@@ -96,8 +96,10 @@ __device__ __forceinline__ T dpp_all(T x)
 {
     const Dw2 w = dw2(x);
     Dw2 r;
-    r.lo = __builtin_amdgcn_update_dpp(w.lo, w.lo, CTRL, 0xf, 0xf, false);
-    r.hi = __builtin_amdgcn_update_dpp(w.hi, w.hi, CTRL, 0xf, 0xf, false);
+    // (every lane of these patterns has a source lane, so no lane keeps an old value: the form without one lets the move read
+    //  its source where it is instead of a copy made for the purpose)
+    r.lo = __builtin_amdgcn_mov_dpp(w.lo, CTRL, 0xf, 0xf, false);
+    r.hi = __builtin_amdgcn_mov_dpp(w.hi, CTRL, 0xf, 0xf, false);
     T y; from_dw2(r, y); return y;
 }
 template <class T> __device__ __forceinline__ T quad_x1(T x) { return dpp_all<0xB1>(x); }
@@ -110,9 +112,9 @@ __device__ __forceinline__ T row_x4(T x)
 {
     const Dw2 w = dw2(x);
     Dw2 r;
-    r.lo = __builtin_amdgcn_update_dpp(w.lo, w.lo, 0x12C, 0xf, 0x5, false);
+    r.lo = __builtin_amdgcn_mov_dpp(w.lo, 0x12C, 0xf, 0x5, false);       // (the other two banks are written by the second move)
     r.lo = __builtin_amdgcn_update_dpp(r.lo, w.lo, 0x124, 0xf, 0xa, false);
-    r.hi = __builtin_amdgcn_update_dpp(w.hi, w.hi, 0x12C, 0xf, 0x5, false);
+    r.hi = __builtin_amdgcn_mov_dpp(w.hi, 0x12C, 0xf, 0x5, false);
     r.hi = __builtin_amdgcn_update_dpp(r.hi, w.hi, 0x124, 0xf, 0xa, false);
     T y; from_dw2(r, y); return y;
 }
@@ -157,6 +159,66 @@ __device__ __forceinline__ T wave_reduce_dpp(T x, Op op)
 __device__ __forceinline__ double wave_sum_dpp(double x) { return wave_reduce_dpp(x, OpAdd()); }
 __device__ __forceinline__ double wave_max_dpp(double x) { return wave_reduce_dpp(x, OpFmax()); }
 __device__ __forceinline__ long long wave_sum_ll_dpp(long long x) { return wave_reduce_dpp(x, OpAdd()); }
+
+// ---- several sums at once: the first two levels transpose them ----
+// v_permlane32_swap on two DIFFERENT registers a, b leaves a = [a's lower half | b's lower half] and b = [a's upper half | b's
+// upper half], so their sum holds a[l] + a[l^32] in lanes 0..31 and b[l] + b[l^32] in lanes 32..63: level 32 of two butterflies
+// for one swap per dword and one addition.  v_permlane16_swap does the same with the rows: the sum holds a's pairs (l, l^16) in
+// the even rows and b's in the odd rows.  The pairs and the order of the levels are those of wave_sum_dpp, and an addition does
+// not care which lane holds which operand, so every total keeps its bits; it ends in one group of lanes instead of all 64.
+__device__ __forceinline__ double swap32_add2(double a, double b)
+{
+    const Dw2 wa = dw2(a), wb = dw2(b);
+    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)wa.lo, (unsigned)wb.lo, false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)wa.hi, (unsigned)wb.hi, false, false);
+    double x, y;
+    from_dw2(Dw2{(int)lo[0], (int)hi[0]}, x);
+    from_dw2(Dw2{(int)lo[1], (int)hi[1]}, y);
+    return x + y;
+}
+__device__ __forceinline__ double swap16_add2(double a, double b)
+{
+    const Dw2 wa = dw2(a), wb = dw2(b);
+    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)wa.lo, (unsigned)wb.lo, false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)wa.hi, (unsigned)wb.hi, false, false);
+    double x, y;
+    from_dw2(Dw2{(int)lo[0], (int)hi[0]}, x);
+    from_dw2(Dw2{(int)lo[1], (int)hi[1]}, y);
+    return x + y;
+}
+// wave_sum_multi<OB>(s, t), OB = 2, 4 or 8, ALL 64 LANES ACTIVE: the OB wave sums of s[0..OB) in wave_sum_multi_regs(OB) registers.
+//   OB = 2: t[0] holds the total of s[0] in lanes 0..31 and of s[1] in lanes 32..63;
+//   OB = 4, 8: row r (lanes 16r..16r+15) of t[j] holds the total of s[4j + 2(r & 1) + (r >> 1)]
+// (wave_sum_multi_index); wave_sum_multi_owner picks one lane of each group, the one that stores the total.
+__host__ __device__ constexpr int wave_sum_multi_regs(int OB) { return OB <= 4 ? 1 : OB / 4; }
+template <int OB> __device__ __forceinline__ uint32_t wave_sum_multi_index(uint32_t lane, int j)
+{
+    const uint32_t row = lane >> 4;
+    return OB == 2 ? row >> 1 : 4u * j + (((row & 1u) << 1) | (row >> 1));
+}
+template <int OB> __device__ __forceinline__ bool wave_sum_multi_owner(uint32_t lane) { return (lane & (OB == 2 ? 31u : 15u)) == 0; }
+template <int OB>
+__device__ __forceinline__ void wave_sum_multi(const double (&s)[OB], double (&t)[wave_sum_multi_regs(OB)])
+{
+    static_assert(OB == 2 || OB == 4 || OB == 8, "pairs of pairs");
+    constexpr int NR = wave_sum_multi_regs(OB);
+    double h[OB / 2];
+#pragma unroll
+    for (int j = 0; j < OB / 2; j++) h[j] = swap32_add2(s[2 * j], s[2 * j + 1]);
+    if constexpr (OB == 2) t[0] = swap16_combine(h[0], OpAdd());
+    else {
+#pragma unroll
+        for (int j = 0; j < NR; j++) t[j] = swap16_add2(h[2 * j], h[2 * j + 1]);
+    }
+#pragma unroll
+    for (int j = 0; j < NR; j++) t[j] += row_x8(t[j]);
+#pragma unroll
+    for (int j = 0; j < NR; j++) t[j] += row_x4(t[j]);
+#pragma unroll
+    for (int j = 0; j < NR; j++) t[j] += quad_x2(t[j]);
+#pragma unroll
+    for (int j = 0; j < NR; j++) t[j] += quad_x1(t[j]);
+}
 
 // A kernel argument the entry block must already hold in scalar registers.  The compiler otherwise sinks each argument's scalar
 // load to the block of its first use, behind every early-out branch: one dependent round trip to the kernarg segment per group of

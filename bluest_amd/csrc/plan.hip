@@ -62,8 +62,21 @@ template <> __device__ __forceinline__ int4 load_cols4<uint16_t>(const uint16_t 
 // run on the VALU (wave_sum_dpp / wave_max_dpp, common.hpp).
 // The slot word of a plan without a slot table is a dummy read of the first four bytes of the column stream (always there: the
 // plan has at least one chunk); its value is discarded, only the absence of a branch around the load matters.
-// What the compiler makes of this prologue is recorded in profiles/r06_isa_counts.txt: re-check it there after a toolchain update.
+// What the compiler makes of this prologue and of the addressing below is recorded in profiles/r07_isa_counts.txt (tools/isa_counts.py):
+// re-check it there after a toolchain update.
 __device__ __forceinline__ bool phi_gate_closed(const int32_t *gate) { return gate && uniform_word(gate) == 0; }
+// Addressing of both chunk kernels: a wavefront's chunk, its output block and every base of vals / cols / m / partial are
+// wave-uniform and live on the SALU; a lane adds one 32-bit byte offset per stream (the loads and the store take the scalar base
+// plus that offset).  What makes 32 bits enough: bluest_plan_finalize refuses plans of more than 0x7fffffff0 entries, so a chunk
+// number and a position in d_partial (one double2 per chunk and candidate) stay below 2^28, and a chunk is at most 1024 * 256
+// entries (2 MiB of values).  Bases are formed in 64 bits.
+// With one wavefront per workgroup (the only launch there is) the chunk is blockIdx.x; the wave number of a wider workgroup
+// has to be read out of the first lane to be scalar for the compiler too.
+template <int WPB> __device__ __forceinline__ uint32_t phi_wave_chunk()
+{
+    if constexpr (WPB == 1) return blockIdx.x;
+    else return blockIdx.x * WPB + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+}
 template <int WPB, typename COLT>
 __global__ __launch_bounds__(64 * WPB) void k_phi_chunks(const double *__restrict__ vals, const COLT *__restrict__ cols,
                                                     int iters, int64_t n_chunks, const double *__restrict__ m,
@@ -73,37 +86,47 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks(const double *__restric
 {
     kernarg_now(vals, cols, iters, n_chunks, m, m_stride, n_cand, partial, pslot, pstride, gate);
     const bool closed = phi_gate_closed(gate);      // device-side predication (SPG line-search slots)
-    const int64_t chunk = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    // where the fold expects this chunk's partial (in flight until the store; the address is valid whatever chunk is)
-    const int32_t slot_ld = *(pslot && chunk < n_chunks ? pslot + chunk : reinterpret_cast<const int32_t *>(cols));
+    const uint32_t chunk = phi_wave_chunk<WPB>();
+    const uint32_t lane = threadIdx.x & 63;
     if (closed) return;
-    if (chunk >= n_chunks) return;
-    const int64_t base = chunk * (int64_t)iters * 256 + lane * 4;
-    for (int c = 0; c < n_cand; c++) {
-        const double *mc = m + (int64_t)c * m_stride;
+    if (chunk >= (uint32_t)n_chunks) return;
+    // where the fold expects this chunk's partial (in flight until the store; both early exits are scalar branches without a
+    // wait of their own, so the load loses nothing behind them)
+    const int32_t slot_ld = *(pslot ? pslot + chunk : reinterpret_cast<const int32_t *>(cols));
+    const uint64_t base = (uint64_t)chunk * ((uint32_t)iters * 256u);      // entries in front of this chunk
+    const char *vb = reinterpret_cast<const char *>(vals + base);
+    const char *cb = reinterpret_cast<const char *>(cols + base);
+    const double *mc = m;
+    char *pc = reinterpret_cast<char *>(partial);
+    for (int c = 0; c < n_cand; c++, mc += m_stride, pc += pstride * (int64_t)sizeof(double2)) {
         double s = 0.0, amax = 0.0;
-        for (int it = 0; it < iters; it++) {
-            const double2 v01 = *reinterpret_cast<const double2 *>(vals + base + it * 256);
-            const double2 v23 = *reinterpret_cast<const double2 *>(vals + base + it * 256 + 2);
-            const int4 cc = load_cols4<COLT>(cols + base + it * 256);
+        uint32_t vo = lane * 32u, co = lane * (uint32_t)(4 * sizeof(COLT));
+        int it = 0;
+        do {      // (a chunk has at least one 256-block)
+            const double2 *vp = reinterpret_cast<const double2 *>(vb + vo);
+            const double2 v01 = vp[0], v23 = vp[1];
+            const int4 cc = load_cols4<COLT>(reinterpret_cast<const COLT *>(cb + co));
             const double m0 = mc[cc.x], m1 = mc[cc.y], m2 = mc[cc.z], m3 = mc[cc.w];
             s = fma(v01.x, m0, s);
             s = fma(v01.y, m1, s);
             s = fma(v23.x, m2, s);
             s = fma(v23.y, m3, s);
             amax = fmax(fmax(amax, fmax(fabs(m0), fabs(m1))), fmax(fabs(m2), fabs(m3)));
-        }
+            vo += 2048u; co += (uint32_t)(256 * sizeof(COLT));
+        } while (++it < iters);
         s = wave_sum_dpp(s);
         amax = wave_max_dpp(amax);
-        const int64_t slot = pslot ? (int64_t)lane_value_here(slot_ld) : chunk;      // the slot load's only wait
-        if (lane == 0) partial[(int64_t)c * pstride + slot] = make_double2(s, amax);
+        const uint32_t slot = pslot ? (uint32_t)lane_value_here(slot_ld) : chunk;      // the slot load's only wait
+        if (lane == 0) *reinterpret_cast<double2 *>(pc + slot * 16u) = make_double2(s, amax);
     }
 }
 
 // Phi pass, shared structure: when every output has the same groups and mapping (the usual multi-output case) the
 // column indices and the gathered m are common; one wavefront streams the chunk of OB outputs and reads them once.
 // vals / partial keep the output-major chunk numbering of the general layout (chunk id = o*ncpo + c).
+// Tail: the OB sums are reduced together (wave_sum_multi, common.hpp: the first two levels transpose them into a quarter as
+// many registers), and the lane that ends with an output's total stores it -- one store instruction per result register.  An
+// output beyond n_out (the tail block streams the last real output again in its place) stores nothing.
 template <int OB, int WPB, typename COLT>
 __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__restrict__ vals, const COLT *__restrict__ cols,
                                                            int iters, int64_t ncpo, int n_out, const double *__restrict__ m,
@@ -112,32 +135,51 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__
 {
     kernarg_now(vals, cols, iters, ncpo, n_out, m, m_stride, n_cand, pstride, pslot, slots_per_output, partial, gate);
     const bool closed = phi_gate_closed(gate);      // device-side predication (SPG line-search slots)
-    const int64_t chunk = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int o0 = blockIdx.y * OB;
-    // where the fold expects this chunk's partials: output-major chunk numbering, or the regular rows' slots (one structure for
-    // all outputs).  In flight until the stores; the address is valid whatever chunk is.
-    const int32_t slot_ld = *(pslot && chunk < ncpo ? pslot + chunk : reinterpret_cast<const int32_t *>(cols));
+    const uint32_t chunk = phi_wave_chunk<WPB>();
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t o0 = blockIdx.y * OB;
     if (closed) return;
-    if (chunk >= ncpo) return;
-    const int64_t ostride = pslot ? (int64_t)slots_per_output : ncpo;
-    const int64_t CH = (int64_t)iters * 256;
-    const int64_t base = chunk * CH + lane * 4;
-    for (int c = 0; c < n_cand; c++) {
-        const double *mc = m + (int64_t)c * m_stride;
+    if (chunk >= (uint32_t)ncpo) return;
+    // where the fold expects this chunk's partials: output-major chunk numbering, or the regular rows' slots (one structure for
+    // all outputs).  In flight until the stores; both early exits are scalar branches without a wait of their own, so the load
+    // loses nothing behind them.
+    const int32_t slot_ld = *(pslot ? pslot + chunk : reinterpret_cast<const int32_t *>(cols));
+    const uint32_t ostride = pslot ? (uint32_t)slots_per_output : (uint32_t)ncpo;
+    const uint32_t CH = (uint32_t)iters * 256u;
+    const char *cb = reinterpret_cast<const char *>(cols + (uint64_t)chunk * CH);
+    // output o0 + oo, clamped to the last one: each base is the one before it plus one output's entries, or the same again
+    const uint64_t per_out = (uint64_t)(uint32_t)ncpo * CH;
+    const char *vb[OB];
+    vb[0] = reinterpret_cast<const char *>(vals + (uint64_t)(o0 * (uint32_t)ncpo + chunk) * CH);
+#pragma unroll
+    for (int oo = 1; oo < OB; oo++) vb[oo] = vb[oo - 1] + (o0 + oo < (uint32_t)n_out ? per_out * sizeof(double) : 0);
+    // this lane's results after wave_sum_multi: which output, and whether this lane stores it
+    constexpr int NR = wave_sum_multi_regs(OB);
+    uint32_t po[NR];
+    bool mine[NR];
+#pragma unroll
+    for (int j = 0; j < NR; j++) {
+        const uint32_t o = o0 + wave_sum_multi_index<OB>(lane, j);
+        mine[j] = wave_sum_multi_owner<OB>(lane) && o < (uint32_t)n_out;
+        po[j] = o * ostride * 16u;
+    }
+    const double *mc = m;
+    char *pc = reinterpret_cast<char *>(partial);
+    for (int c = 0; c < n_cand; c++, mc += m_stride, pc += pstride * (int64_t)sizeof(double2)) {
         double s[OB];
 #pragma unroll
         for (int oo = 0; oo < OB; oo++) s[oo] = 0.0;
         double amax = 0.0;
-        for (int it = 0; it < iters; it++) {
-            const int4 cc = load_cols4<COLT>(cols + base + it * 256);
+        uint32_t vo = lane * 32u, co = lane * (uint32_t)(4 * sizeof(COLT));
+        int it = 0;
+        do {      // (a chunk has at least one 256-block)
+            const int4 cc = load_cols4<COLT>(reinterpret_cast<const COLT *>(cb + co));
             double2 v01[OB], v23[OB];
 #pragma unroll
             for (int oo = 0; oo < OB; oo++) {
-                const int o = (o0 + oo < n_out) ? o0 + oo : n_out - 1;
-                const double *vp = vals + (int64_t)o * ncpo * CH + base + it * 256;
-                v01[oo] = *reinterpret_cast<const double2 *>(vp);
-                v23[oo] = *reinterpret_cast<const double2 *>(vp + 2);
+                const double2 *vp = reinterpret_cast<const double2 *>(vb[oo] + vo);
+                v01[oo] = vp[0];
+                v23[oo] = vp[1];
             }
             const double m0 = mc[cc.x], m1 = mc[cc.y], m2 = mc[cc.z], m3 = mc[cc.w];
             amax = fmax(fmax(amax, fmax(fabs(m0), fabs(m1))), fmax(fabs(m2), fabs(m3)));
@@ -148,16 +190,15 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__
                 s[oo] = fma(v23[oo].x, m2, s[oo]);
                 s[oo] = fma(v23[oo].y, m3, s[oo]);
             }
-        }
+            vo += 2048u; co += (uint32_t)(256 * sizeof(COLT));
+        } while (++it < iters);
         amax = wave_max_dpp(amax);
-        const int64_t slot = pslot ? (int64_t)lane_value_here(slot_ld) : chunk;      // the slot load's only wait
-        // (the OB sums one behind the other, each stored as it is ready: reducing them as interleaved chains with the stores
-        //  afterwards measured no faster once they were DPP chains, profiles/r06_step_parts_ablation.txt)
+        double t[NR];
+        wave_sum_multi<OB>(s, t);
+        const uint32_t slot = pslot ? (uint32_t)lane_value_here(slot_ld) : chunk;      // the slot load's only wait
 #pragma unroll
-        for (int oo = 0; oo < OB; oo++) {
-            const double t = wave_sum_dpp(s[oo]);
-            if (lane == 0 && o0 + oo < n_out) partial[(int64_t)c * pstride + (int64_t)(o0 + oo) * ostride + slot] = make_double2(t, amax);
-        }
+        for (int j = 0; j < NR; j++)
+            if (mine[j]) *reinterpret_cast<double2 *>(pc + (po[j] + slot * 16u)) = make_double2(t[j], amax);
     }
 }
 
@@ -1339,6 +1380,8 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
     timer.lap("CSR slots + columns");
     layout_invmap(plan, lay);
     plan->cols16 = plan->L <= 65536 && getenv("BLUEST_COLS32") == nullptr;       // (A/B switch: BLUEST_COLS32=1 keeps int32 columns)
+    plan->phi_ob_forced = 0;                                                      // (A/B switch: BLUEST_PHI_OB=2|4|8, see phi_ob)
+    if (const char *e = getenv("BLUEST_PHI_OB")) { const int v = atoi(e); if (v == 2 || v == 4 || v == 8) plan->phi_ob_forced = v; }
     plan->phi_bytes = plan->n_chunks * lay.CH * 8 + (plan->shared ? plan->n_chunks / n_out : plan->n_chunks) * lay.CH * (plan->cols16 ? 2 : 4) + plan->n_chunks * 16;
     plan->grad_bytes = (int64_t)lay.n_tvals * 8 + plan->grad_len * 8;
     const char *nt_env = getenv("BLUEST_TILE_NT");              // A/B switch, read per plan: 0 = plain loads
@@ -1524,17 +1567,29 @@ static void launch_solve_grad(bluest_plan_t plan, const double *rec, double delt
     }); });
 }
 
-// outputs per wavefront of the shared Phi pass (k_phi_chunks_shared<OB>), 0: the plain k_phi_chunks.  Sharing the column stream
-// saves bytes, but the pass is latency-bound, so keep at least ~4096 wavefronts in flight (measured at n=20, n_out=8: OB=8 6.9 us,
-// OB=4 5.5 us, OB=2 5.1 us, OB=1 6.1 us): the widest OB of PhiObSet that does, else the narrowest
-static int phi_ob(const bluest_plan_s *p)
+// outputs per wavefront of the shared Phi pass (k_phi_chunks_shared<OB>) for a launch of n_cand candidates, 0: the plain
+// k_phi_chunks.  A wider OB reads the column stream and gathers m once for more outputs and spends fewer instructions per output
+// (profiles/r07_isa_counts.txt), but leaves fewer wavefronts to hide the latency of the stream behind.
+// One candidate: the widest OB of PhiObSet that keeps PHI_MIN_WAVES wavefronts, else the narrowest.  The 2304 (nine wavefronts per
+// compute unit) rests on ONE shape: at the headline size (1160 chunks per output, 8 outputs) OB = 4 with 2320 wavefronts takes
+// 3.3-3.4 us against 4.1-4.2 us of OB = 2 with 4640 (profiles/r07_step_parts_ab.txt), and nothing was measured between 2080
+// wavefronts -- where the plans of tests/test_gpu_launch_matrix.py keep the narrower OB -- and 2320.  (The 4096 that stood here before
+// was measured in round 3 with six ds_bpermute trips per sum in the tail: OB = 8 6.9 us, 4 5.5 us, 2 5.1 us, 1 6.1 us.)
+// A batch (n_cand > 1) takes the same OB: every wavefront loops over the candidates, and the m gathers that bound the pass are
+// repeated per block of outputs, so a wider OB pays more there (n_cand = 16 at the headline size: 28 us at OB = 4 against 42 us at
+// OB = 2), but the widest is not the best one -- OB = 8 with 1160 wavefronts takes 32 us (profiles/r07_batch_ob.txt).
+// BLUEST_PHI_OB (read per plan at finalize) forces an OB for shared plans of two or more outputs: an A/B switch.
+static const int64_t PHI_MIN_WAVES = 2304;
+static int phi_ob(const bluest_plan_s *p, int n_cand)
 {
+    (void)n_cand;      // one rule for every n_cand, see above; launch_chunks and bluest_plan_launch_config both ask here
     const int n_out = (int)p->outs.size();
     if (!p->shared || n_out < 2) return 0;
+    if (p->phi_ob_forced) return p->phi_ob_forced;
     const int64_t ncpo = p->n_chunks / n_out;
     for (int i = PhiObSet::count - 1; i > 0; i--) {
         const int ob = PhiObSet::values[i];
-        if (ob <= n_out && ncpo * ((n_out + ob - 1) / ob) >= 4096) return ob;
+        if (ob <= n_out && ncpo * ((n_out + ob - 1) / ob) >= PHI_MIN_WAVES) return ob;
     }
     return PhiObSet::values[0];
 }
@@ -1544,7 +1599,7 @@ static void launch_chunks(bluest_plan_t p, const double *m, int n_cand, int64_t 
     const int n_out = (int)p->outs.size();
     // one wavefront per workgroup of the chunk kernels (WPB = 1): single-wavefront workgroups drain earliest at the kernel's end
     // (same-box A/B at the headline size, two runs each: step 12.86 / 12.26 / 12.05 us with 4 / 2 / 1 wavefronts, 13.8 with 16)
-    if (const int ob = phi_ob(p)) {
+    if (const int ob = phi_ob(p, n_cand)) {
         const int64_t ncpo = p->n_chunks / n_out;
         PhiObSet::dispatch(ob, [&](auto obc) {
             constexpr int OB = decltype(obc)::value;
@@ -1750,7 +1805,7 @@ extern "C" int bluest_plan_launch_config(bluest_plan_t plan, int n_cand, int32_t
     std::fill(cfg, cfg + BLUEST_LC_COUNT, 0);
     const bool one = n_cand == 1 && !plan->gate;
     cfg[BLUEST_LC_PATH] = (one && plan->matfree) ? 2 : (one && plan->mf_gradient) ? 3 : (n_cand == 1) ? 1 : 0;
-    cfg[BLUEST_LC_PHI_OB] = phi_ob(plan);
+    cfg[BLUEST_LC_PHI_OB] = phi_ob(plan, n_cand);
     cfg[BLUEST_LC_COLS16] = plan->cols16 ? 1 : 0;
     nt_dispatch(plan->N, [&](auto nt) {
         cfg[BLUEST_LC_NT] = decltype(nt)::value;

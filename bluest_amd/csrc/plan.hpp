@@ -62,6 +62,7 @@ struct bluest_plan_s {
     double *d_vals = nullptr;
     int32_t *d_cols = nullptr;          // columns of the Phi layout; holds uint16 entries when cols16 (allocation vectors of <= 65 536 entries)
     bool cols16 = false;
+    int phi_ob_forced = 0;              // BLUEST_PHI_OB=2|4|8 at finalize (A/B switch): OB of the shared Phi pass, 0: phi_ob()'s rule
     RowDesc *d_rows = nullptr;
     TileDesc *d_tiles = nullptr;
     double *d_tvals = nullptr;   // tiles: slot pairs (see TileDesc)

@@ -401,6 +401,10 @@ int bluest_launch_set(int axis, int32_t *values, int cap, int *n);
  * (int64) the integer wave sum of the rows' bit patterns shifted right by 8 (so that nothing overflows). */
 int bluest_wave_reduce_probe(const double *in_dev, int64_t n_rows, double *sum_dev, double *max_dev, double *quad_dev,
                              int64_t *isum_dev, void *stream);
+/* Diagnostic: wave_sum_multi of csrc/common.hpp, the reduction of ob = 2, 4 or 8 sums at once in the tail of k_phi_chunks_shared.
+ * in_dev is n_rows x ob x 64 doubles, one wavefront per row; out_dev (n_rows x ob) receives each vector's wave sum, written by the
+ * lane that kernel stores it from. */
+int bluest_wave_reduce_multi_probe(const double *in_dev, int64_t n_rows, int ob, double *out_dev, void *stream);
 /* m_i = cc_i ((1 - eps) x_S[i in S] + eps / L); sup_dev ascending */
 int bluest_support_point(int64_t L, int S, const int64_t *sup_dev, const double *xs_dev, const double *cc_dev, double eps,
                          double *m_dev, void *stream);
