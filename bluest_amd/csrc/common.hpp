@@ -231,3 +231,6 @@ template <class T, class... R> __device__ __forceinline__ void kernarg_now(const
 __device__ __forceinline__ int32_t uniform_word(const int32_t *p) { return *(const __attribute__((address_space(4))) int32_t *)p; }
 // a lane value the optimiser must take as it is HERE: keeps a load's first use (and its wait) where the code puts it
 template <class T> __device__ __forceinline__ T lane_value_here(T x) { asm volatile("" : "+v"(x)); return x; }
+// the same for a wave-uniform value in a scalar register: what is computed from it stays behind this point (a rarely taken
+// branch keeps its own comparisons instead of having them hoisted, and their results spilled, in front of the common path)
+template <class T> __device__ __forceinline__ T uniform_value_here(T x) { asm volatile("" : "+s"(x)); return x; }

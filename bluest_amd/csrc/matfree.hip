@@ -369,7 +369,7 @@ __global__ __launch_bounds__(64 * (MF_TILE_WAVES + 1)) void k_solve_grad_mf(cons
     if (N < NT) { clear_pads(lds, N, tid, NTHREADS); __syncthreads(); }
     for (int t = tid; t < N * N; t += NTHREADS) mf_cs[t] = A.C[(int64_t)o * N * N + t];
     if (rec_o) { for (int t = tid; t < N * N; t += NTHREADS) lds.at(t / N, t % N) = rec_o[t]; }
-    else fold_rows<NT>(lds, N, rows, o * A.nsym, A.nsym, partial, tid, NTHREADS, reg);
+    else fold_rows<NT>(lds, N, rows, o, A.nsym, partial, tid, NTHREADS, reg);
     const int t_mine = A.tile_begin[o] + b * MF_TILE_WAVES + wave - 1;
     MfTile td;
     td.first = 0; td.n = 0; td.k = 0;

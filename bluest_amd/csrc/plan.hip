@@ -241,7 +241,7 @@ __global__ __launch_bounds__(fold_threads(NT)) void k_solve_from_chunks(int N, i
     SpgPrefetch pf;
     if (spg_state && tid < WAVE) spg_prefetch_state(spg_state, tid, pf);   // in flight during the fold (see spg_state.hpp)
     if (N < NT) { clear_pads(lds, N, tid, fold_threads(NT)); __syncthreads(); }   // uniform; every real entry is written by the fold
-    fold_rows(lds, N, rows, o * nsym, nsym, partial + (int64_t)c * n_chunks, tid, fold_threads(NT), reg);
+    fold_rows(lds, N, rows, o, nsym, partial + (int64_t)c * n_chunks, tid, fold_threads(NT), reg);
     __syncthreads();
     if (tid >= WAVE) return;   // single wavefront from here on
     const int lane = tid;
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(fold_threads(NT)) void k_fold_to_record(int N, int 
     __shared__ SolveLds<NT> lds;
     kernarg_now(N, n_out, rows, nsym, reg.Cd, reg.Co, reg.rank_ab, partial, n_chunks, rec);      // one batch (common.hpp)
     const int o = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
-    fold_rows(lds, N, rows, o * nsym, nsym, partial + (int64_t)c * n_chunks, tid, fold_threads(NT), reg);
+    fold_rows(lds, N, rows, o, nsym, partial + (int64_t)c * n_chunks, tid, fold_threads(NT), reg);
     __syncthreads();
     const int reclen = N * N + 2 * N + 1;
     double *r = rec + ((int64_t)c * n_out + o) * reclen;
@@ -468,16 +468,19 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
     constexpr int PU = tile_pairs(KU);
     __shared__ SolveLds<NT> lds;
     __shared__ double spg_ls[SPG_STATE_DOUBLES];
-    // everything in front of the fold's first load arrives in one batch (kernarg_now, common.hpp); the tile stream's arguments
-    // and the outputs may follow while the fold is in flight
-    kernarg_now(N, n_out, rows, nsym, reg.Cd, reg.Co, reg.rank_ab, partial, rec, tiles, bpo, tpb, gate, spg_state);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int64_t t0 = (int64_t)blockIdx.x * tpb;      // tpb <= FUSED_TPB tiles per workgroup (wavefronts beyond it only fold)
-    // which output, and am I its first workgroup: arithmetic when every output has the same number of workgroups (bpo > 0,
-    // the usual case), else from the first tile's descriptor (one more dependent load in front of the fold)
-    int o, first;
-    if (bpo > 0) { o = blockIdx.x / bpo; first = (blockIdx.x % bpo) == 0; }
-    else { const TileDesc td0 = tiles[t0]; o = td0.out; first = (td0.n_valid >> 30) & 1; }
+    // everything in front of the fold's first load arrives in one batch (kernarg_now, common.hpp), and with it what the solving
+    // wavefront would otherwise fetch behind the barrier, one scalar round trip each on the path everybody waits for: delta and
+    // the three outputs it writes; the tile stream's arguments may follow while the fold is in flight
+    kernarg_now(N, n_out, rows, nsym, reg.Cd, reg.Co, reg.rank_ab, partial, rec, tiles, bpo, tpb, gate, spg_state, delta, var, v_ws, status);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (the compiler does not see that tid >> 6 is wave-uniform)
+    // which output, and am I its first workgroup: the grid says so when every output has the same number of workgroups (bpo > 0,
+    // the usual case: grid = (bpo, n_out), no division), else the first tile's descriptor (grid = (workgroups, 1); one more
+    // dependent load in front of the fold)
+    int o, first, wg;
+    if (bpo > 0) { o = blockIdx.y; first = blockIdx.x == 0; wg = o * bpo + blockIdx.x; }
+    else { wg = blockIdx.x; const TileDesc td0 = tile_desc_uniform(tiles, (int64_t)wg * tpb); o = td0.out; first = (td0.n_valid >> 30) & 1; }
+    const int64_t t0 = (int64_t)wg * tpb;      // tpb <= FUSED_TPB tiles per workgroup (wavefronts beyond it only fold)
     __shared__ int s_closed;
     if (gate_closed(gate, &s_closed)) {
         // predicated off; the line-search decision still has to close the slot (see k_solve_from_chunks): the first workgroups
@@ -500,13 +503,15 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
     if (rec_o) {
         for (int t = tid; t < N * N; t += NTHREADS) lds.at(t / N, t % N) = rec_o[t];
     } else {
-        fold_rows<NT>(lds, N, rows, o * nsym, nsym, partial, tid, NTHREADS, reg);
+        fold_rows<NT>(lds, N, rows, o, nsym, partial, tid, NTHREADS, reg);
     }
     // the list is padded to a multiple of FUSED_TPB tiles per output, so every tile of this workgroup belongs to output o
-    // (loaded by the tile wavefronts only: the solving wavefront must not wait for a descriptor it does not use)
+    // (loaded by the tile wavefronts only: the solving wavefront must not wait for a descriptor it does not use; scalar loads, so
+    //  k, the offsets and the group count are scalar: the dispatch on k branches, the tile's and the gradient's bases are formed
+    //  on the scalar unit and a lane adds a 32-bit offset)
     TileDesc td;
     td.k = 1; td.n_valid = 0; td.val_off = td.grad_off = 0; td.out = (int16_t)o;
-    if (wave > 0 && wave <= tpb) td = tiles[t0 + wave - 1];
+    if (wave > 0 && wave <= tpb) td = tile_desc_uniform(tiles, t0 + wave - 1);
     __syncthreads();
     const int k = td.k;
     double2 pr[PU];
@@ -536,8 +541,8 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
         }
     } else if (k <= KU) {
         // stream the tile into registers while wavefront 0 factorises (after the fold, so these loads do not queue in front of it)
-        if (tile_nt) tile_load<PU, true>(pr, tvals + td.val_off + 2 * lane, tile_pairs(k));
-        else tile_load(pr, tvals + td.val_off + 2 * lane, tile_pairs(k));
+        if (tile_nt) tile_load<PU, true>(pr, tvals + td.val_off, lane, tile_pairs(k));
+        else tile_load(pr, tvals + td.val_off, lane, tile_pairs(k));
     }
     __syncthreads();
     if (wave == 0) {
@@ -1558,7 +1563,8 @@ static void launch_solve_grad(bluest_plan_t plan, const double *rec, double delt
                               double *dec_state, int dec_last, int32_t *dec_enable, MaTail ma, hipStream_t st)
 {
     const int n_out = (int)plan->outs.size();
-    const dim3 grid((unsigned)(plan->n_tiles / plan->fused_tpb));
+    // (bpo, n_out) when every output has bpo workgroups -- the kernel reads its output off the grid --, else one row of workgroups
+    const dim3 grid = plan->fused_bpo > 0 ? dim3((unsigned)plan->fused_bpo, (unsigned)n_out) : dim3((unsigned)(plan->n_tiles / plan->fused_tpb));
     nt_dispatch(plan->N, [&](auto nt) { solve_grad_ku_dispatch(plan->kmax, [&](auto ku) {
         constexpr int NT = decltype(nt)::value, KU = decltype(ku)::value;
         hipLaunchKernelGGL((k_solve_grad<NT, KU>), grid, dim3(64 * (fused_tpb(NT, KU) + 1)), 0, st, plan->N, n_out, plan->d_rows, plan->nsym,

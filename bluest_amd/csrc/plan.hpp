@@ -20,6 +20,19 @@ __host__ __device__ constexpr int tile_pairs(int k) { return tile_slots(k) / 2; 
 // offset (doubles, relative to the tile) of slot sl of lane l
 __host__ __device__ constexpr int64_t tile_slot_off(int sl, int lane) { return (int64_t)(sl >> 1) * 128 + lane * 2 + (sl & 1); }
 
+// descriptor t through scalar loads into scalar registers; t must be wave-uniform.  (The descriptors are written at set-up and
+// by nobody afterwards; the constant address space is what lets the load be a scalar one behind a kernarg_now, see uniform_word.)
+__device__ __forceinline__ TileDesc tile_desc_uniform(const TileDesc *__restrict__ tiles, int64_t t)
+{
+    static_assert(sizeof(TileDesc) == 24, "three 64-bit words");
+    const auto *w = (const __attribute__((address_space(4))) uint64_t *)(tiles + t);
+    const uint64_t w0 = w[0], w1 = w[1], w2 = w[2];
+    TileDesc td;
+    td.val_off = (int64_t)w0; td.grad_off = (int64_t)w1; td.n_valid = (int32_t)(uint32_t)w2;
+    td.k = (int16_t)(uint16_t)(w2 >> 32); td.out = (int16_t)(uint16_t)(w2 >> 48);
+    return td;
+}
+
 
 struct OutputDesc {
     int K = 0;
@@ -107,13 +120,18 @@ struct DeviceScope {
 // the slot pairs of one lane's group, PU pairs of registers (PU >= tile_pairs(K)); loaded with 16-byte loads
 typedef double tile_d2v __attribute__((ext_vector_type(2)));
 template <int PU, bool NT = false>
-__device__ __forceinline__ void tile_load(double2 (&pr)[PU], const double *__restrict__ tile_lane, int n_pairs)
-{   // tile_lane = tvals + td.val_off + 2 * lane; NT: non-temporal loads (the fused kernel's stream, see bluest_plan_s::tile_nt)
+__device__ __forceinline__ void tile_load(double2 (&pr)[PU], const double *__restrict__ tile, int lane, int n_pairs)
+{   // tile = tvals + td.val_off; NT: non-temporal loads (the fused kernel's stream, see bluest_plan_s::tile_nt).  The lane's
+    // offset is ONE 32-bit byte offset for the first four pairs (an instruction's own offset ends below 4096; behind them the
+    // compiler folds the 4096 into a 64-bit lane address), so a wave-uniform tile keeps its base in scalar registers
+    const char *base = reinterpret_cast<const char *>(tile);
+    const uint32_t lo = 16u * (uint32_t)lane;
 #pragma unroll
     for (int i = 0; i < PU; i++)
         if (i < n_pairs) {
-            if (NT) { const tile_d2v v = __builtin_nontemporal_load(reinterpret_cast<const tile_d2v *>(tile_lane + i * 128)); pr[i] = make_double2(v.x, v.y); }
-            else pr[i] = *reinterpret_cast<const double2 *>(tile_lane + i * 128);
+            const char *p = (base + (lo + 4096u * (i >> 2))) + 1024 * (i & 3);
+            if (NT) { const tile_d2v v = __builtin_nontemporal_load(reinterpret_cast<const tile_d2v *>(p)); pr[i] = make_double2(v.x, v.y); }
+            else pr[i] = *reinterpret_cast<const double2 *>(p);
         }
 }
 template <int PU>
@@ -127,9 +145,10 @@ __device__ __forceinline__ double tile_form(const double2 (&pr)[PU], const doubl
     constexpr int NI = tile_ni(K);
     double vj[K];
 #pragma unroll
-    for (int j = 0; j < K; j++) {
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(tile_slot(pr, j >> 3));
-        vj[j] = vc[(int)((bits >> (8 * (j & 7))) & 0xffull)];
+    for (int j = 0; j < K; j++) {      // model j of the group: byte j & 7 of index slot j >> 3, taken from the dword that holds it
+        const double sl = tile_slot(pr, j >> 3);
+        const unsigned w = (unsigned)((j & 4) ? __double2hiint(sl) : __double2loint(sl));
+        vj[j] = vc[(w >> (8 * (j & 3))) & 0xffu];
     }
     double q = 0.0;
     int e = NI;
@@ -152,7 +171,7 @@ __device__ __forceinline__ void grad_tile(const TileDesc &td, const double *__re
                                           double *__restrict__ grad, int64_t grad_stride, int lane)
 {
     double2 pr[tile_pairs(K)];
-    tile_load(pr, tvals + td.val_off + 2 * lane, tile_pairs(K));
+    tile_load(pr, tvals + td.val_off, lane, tile_pairs(K));
     for (int c = 0; c < n_cand; c++) {
         const int64_t eo = (int64_t)c * n_out + td.out;
         const double q = tile_form<K>(pr, v + eo * N);

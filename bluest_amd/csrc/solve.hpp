@@ -77,7 +77,7 @@ __device__ __forceinline__ double fast_max(double v)
     v = fmax(v, dpp_f64<0x140>(v));
     return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)), fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
 }
-// fold chunk partials of rows [row_begin, row_begin+n_rows) into lds.phi / lds.amax; all threads of the block.
+// fold chunk partials of the n_rows rows of output o (wave-uniform) into lds.phi / lds.amax; all threads of the block.
 // FOUR adjacent lanes share a row: lane q sums chunks q, q+4, q+8, ... (up to 8 independent loads in flight, so a row of
 // <= 32 chunks costs ONE memory round trip), then the quad combines as (s0+s1)+(s2+s3) -- a fixed order, so the result
 // is deterministic and identical in every kernel that folds -- with quad_perm DPP moves (common.hpp; the lanes of a quad share
@@ -99,13 +99,13 @@ __device__ __forceinline__ double opaque_zero()
 // (descriptor -> partials), measured 0.47 us of the 1.5 us fold at the headline size.  Cd = 0: the descriptor path.
 struct FoldReg { int Cd, Co; const uint16_t *rank_ab; };     // rank_ab[r] = a | b << 8 of the destination with rank r
 template <int NT>
-__device__ __forceinline__ void fold_rows(SolveLds<NT> &lds, int N, const RowDesc *__restrict__ rows, int row_begin,
+__device__ __forceinline__ void fold_rows(SolveLds<NT> &lds, int N, const RowDesc *__restrict__ rows, int o,
                                           int n_rows, const double2 *__restrict__ partial, int tid, int nthreads, FoldReg reg)
-{
+{   // the output's rows are rows[o * n_rows ..) and, regular, its partials partial[o * slots ..): no division by n_rows
     const int q = tid & 3;
     if (reg.Cd > 0) {
         const int slots = N * reg.Cd + (n_rows - N) * reg.Co;
-        const double2 *po = partial + (int64_t)(row_begin / n_rows) * slots;
+        const double2 *po = partial + (int64_t)o * slots;
         for (int r = tid >> 2; r < n_rows; r += nthreads >> 2) {
             const bool dg = r < N;
             const int n = dg ? reg.Cd : reg.Co;
@@ -133,7 +133,7 @@ __device__ __forceinline__ void fold_rows(SolveLds<NT> &lds, int N, const RowDes
         return;
     }
     for (int r = tid >> 2; r < n_rows; r += nthreads >> 2) {
-        const RowDesc rd = rows[row_begin + r];
+        const RowDesc rd = rows[o * n_rows + r];
         const double2 *p = partial + rd.first_chunk;
         const int n = rd.n_chunks;
         double s = opaque_zero(), am = opaque_zero();
@@ -413,18 +413,20 @@ __device__ __forceinline__ void solve_wave(SolveLds<NT> &lds, int N, double delt
             }
             const unsigned long long smask = mask;                      // bit i: model at position NT-1-i is in the system
             if (__builtin_expect(smask != all, 0)) {
+                const int Nh = uniform_value_here(N);      // (or the NT comparisons with N are made, and spilled, in front of every solve)
 #pragma unroll
                 for (int c = 0; c < NT; c++) {
-                    const bool colin = (NT - 1 - c) < N && ((smask >> (NT - 1 - c)) & 1ull);
+                    const bool colin = (NT - 1 - c) < Nh && ((smask >> (NT - 1 - c)) & 1ull);
                     a[c] = (mine && colin) ? a[c] : 0.0;
                 }
             }
             const double diag = mine ? delta : 1.0;                     // pads / unsampled models: identity row
             double diag0 = 1.0;                                         // my original diagonal entry (lanes >= NT: unused)
+            const int ph = lane_value_here(p);      // (or the NT comparisons with p are made in front of the passes and their results spilled)
 #pragma unroll
             for (int c = 0; c < NT; c++) {
-                a[c] = (c == p) ? a[c] + diag : a[c];
-                diag0 = (c == p) ? a[c] : diag0;
+                a[c] = (c == ph) ? a[c] + diag : a[c];
+                diag0 = (c == ph) ? a[c] : diag0;
             }
             double last_pivot = 1.0;
             int bad = 0;

@@ -8,7 +8,9 @@ Static instruction counts of the evaluation step's kernels from a device listing
 Per Phi kernel: all instructions of the listing (every block once -- which is what a wavefront executes when iters = 1 and
 n_cand = 1, minus the block a branch skips), split into VALU / SALU / VMEM / SMEM, the instructions in front of the first
 streaming load, those behind the loop's last FMA (the tail), the waits in front of the stream, and the registers.
-For k_solve_grad<20,5>: the line numbers (relative to the kernel's start) of the descriptor load, the late kernarg loads, the
+For k_solve_grad<20,5>: the instruction counts of four regions (solve_regions: entry -> first fold load along the shortest path,
+the fold, the tile stream and the solving wavefront between the barriers, the tile wavefronts behind the second barrier) and the
+registers; then the line numbers (relative to the kernel's start) of the descriptor load, the late kernarg loads, the
 first load of the fold, the barriers and the first non-temporal tile load, with the waits between the first barrier and that load.
 """
 import re
@@ -24,9 +26,10 @@ def kernel_body(lines, prefix):
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
     meta = {}
     for l in lines[end:end + 120]:
-        m = re.match(r"\s*;\s*(NumVgprs|NumSgprs|Occupancy|ScratchSize|NumAgprs):\s*(\d+)", l)
+        m = re.match(r"\s*;\s*(NumVgprs|NumSgprs|TotalNumSgprs|Occupancy|ScratchSize|NumAgprs):\s*(\d+)", l)
         if m:
             meta[m.group(1)] = int(m.group(2))
+    meta.setdefault("NumSgprs", meta.get("TotalNumSgprs", -1))
     return start, [l for l in lines[start + 1:end + 1]], meta
 
 
@@ -92,12 +95,104 @@ def solve_report(name, body):
             print("          " + x)
 
 
+def blocks_of(body):
+    """basic blocks of a kernel's text: list of (labels, [instructions]); a block ends behind a branch or s_endpgm, or in front of a label"""
+    out, labels, cur = [], [], []
+    for l in body:
+        t = l.strip()
+        m = re.match(r"^([.\w$]+):", t)
+        if m:
+            if cur:
+                out.append((labels, cur))
+                labels, cur = [], []
+            labels.append(m.group(1))
+            continue
+        if not t or t.startswith((";", ".", "//")):
+            continue
+        ins = t.split(";")[0].strip()
+        cur.append(ins)
+        if ins.startswith(("s_cbranch", "s_branch", "s_endpgm")):
+            out.append((labels, cur))
+            labels, cur = [], []
+    if cur:
+        out.append((labels, cur))
+    return out
+
+
+def tally(ins):
+    n = {k: 0 for k in ("VALU", "SALU", "VMEM", "SMEM", "LDS")}
+    for i in ins:
+        n[kind(i)] += 1
+    return "%4d  (VALU %4d  SALU %4d  VMEM %3d  SMEM %2d  LDS %3d)" % (len(ins), n["VALU"], n["SALU"], n["VMEM"], n["SMEM"], n["LDS"])
+
+
+def solve_regions(name, body, meta):
+    """k_solve_grad in four regions.  (1) entry -> the regular fold's first partial load: the SHORTEST path through the kernel's
+    blocks that meets no vector load, LDS operation or barrier on its way -- what a wavefront of a plan without a gate, with equal
+    workgroups per output, no pads and no record executes.  (2) the fold: the text from that load to the barrier behind it, every
+    instruction once (all eight slot counts of the regular fold are in it; a wavefront runs one of them).  (3) between that barrier
+    and the next: the tile wavefronts' stream (up to the last 16-byte load) and the solving wavefront (the rest: every pass and
+    rare path of solve_wave once).  (4) behind the second barrier: the tile wavefronts' forms and stores, all group sizes."""
+    bl = blocks_of(body)
+    flat = [(b, j) for b, (_, ins) in enumerate(bl) for j in range(len(ins))]
+    text = [bl[b][1][j] for b, j in flat]
+    ush = next(i for i, x in enumerate(text) if x.startswith("global_load_ushort"))
+    first = next(i for i in range(ush, len(text)) if text[i].startswith("global_load_dwordx4"))
+    tb, tj = flat[first]
+    label_block = {lab: b for b, (labs, _) in enumerate(bl) for lab in labs}
+    clean = lambda ins: not any(x.startswith(("global_", "flat_", "buffer_", "ds_", "s_barrier")) and      # noqa: E731
+                                not x.startswith("global_load_ushort") for x in ins)      # (the row's rank_ab load belongs to the fold)
+    # shortest path over blocks, cost = instructions executed
+    import heapq
+    dist, heap = {0: 0}, [(0, 0, [0])]
+    best = None
+    while heap:
+        d, b, path = heapq.heappop(heap)
+        if b == tb:
+            best = (d, path)
+            break
+        if d > dist.get(b, 1 << 30) or not clean(bl[b][1]):
+            continue
+        ins = bl[b][1]
+        last = ins[-1]
+        succ = []
+        if last.startswith("s_endpgm"):
+            continue
+        if last.startswith(("s_branch", "s_cbranch")):
+            succ.append(label_block[last.split()[-1]])
+        if not last.startswith("s_branch") and b + 1 < len(bl):
+            succ.append(b + 1)
+        for nb in succ:
+            nd = d + len(ins)
+            if nd < dist.get(nb, 1 << 30):
+                dist[nb] = nd
+                heapq.heappush(heap, (nd, nb, path + [nb]))
+    print(name + "   VGPRs %d  SGPRs %d  scratch %d  occupancy %d" % (meta.get("NumVgprs", -1), meta.get("NumSgprs", -1),
+                                                                     meta.get("ScratchSize", -1), meta.get("Occupancy", -1)))
+    if best is None:
+        print("   (1) entry -> first fold load: no path without a vector load, an LDS operation or a barrier")
+    else:
+        head = [x for b in best[1][:-1] for x in bl[b][1]] + bl[tb][1][:tj]
+        print("   (1) entry -> first fold load        %s   waits on the way: %s" % (
+            tally(head), ", ".join(x.replace("s_waitcnt ", "") for x in head if x.startswith("s_waitcnt")) or "none"))
+    bar = [i for i, x in enumerate(text) if x.startswith("s_barrier")]
+    b1 = next(i for i in bar if i > first)
+    b2 = next(i for i in bar if i > b1)
+    print("   (2) fold, first load -> barrier      %s" % tally(text[first:b1]))
+    tl = max(i for i in range(b1, b2) if text[i].startswith("global_load_dwordx4"))
+    print("   (3) tile stream behind the barrier   %s" % tally(text[b1 + 1:tl + 1]))
+    print("       solving wavefront -> 2nd barrier %s" % tally(text[tl + 1:b2]))
+    print("   (4) behind the second barrier        %s" % tally(text[b2 + 1:]))
+    print("       whole kernel                     %s" % tally(text))
+
+
 def main():
     lines = open(sys.argv[1]).read().split("\n")
     for name, prefix in PHI:
         _, body, meta = kernel_body(lines, prefix)
         phi_report(name, body, meta)
-    _, body, _ = kernel_body(lines, SOLVE[1])
+    _, body, meta = kernel_body(lines, SOLVE[1])
+    solve_regions(SOLVE[0], body, meta)
     solve_report(SOLVE[0], body)
 
 
