@@ -4,9 +4,12 @@ exported by the reference's package next to SAP / MOSAP / BLUEProblem, bluest/__
 
 Host Python around the user's model: nothing here is on the accelerated path (SURVEY.md section 2 lists sampling as out of scope),
 so this is the plain accumulation -- sums of the outputs and of their pairwise inner products, cost = evaluation time unless the
-problem states its own -- with the reference's argument names.  The sample files (`filename`, `outputs_to_save`) and the MLMC
-difference sums (`compute_mlmc_differences`) belong to the reference's covariance-estimation / MLMC drivers, which this build
-refuses (BLUEProblem._out_of_scope), and are refused here too.
+problem states its own -- with the reference's argument names.  With `compute_mlmc_differences=True` it also returns the sums
+of the differences y_i - y_j and of their inner products with themselves (i < j), formed from the explicit differences as
+blue_fn.py:147-157 forms them: the 5-tuple the covariance estimation of bluest_amd.pilot.PilotMixin takes when the problem
+overrides `get_models_inner_products` (inner products written in Python cannot run on the GPU; for scalar outputs the mix-in
+uses the kernel behind bluest_amd.pilot.pilot_statistics instead).  The sample files (`filename`, `outputs_to_save`) stay
+refused.
 """
 import time
 from inspect import signature
@@ -28,13 +31,14 @@ def _all_finite(values):
 
 def blue_fn(ls, N, problem, sampler=None, inners=None, comm=None, N1=1, No=1, verbose=True, compute_mlmc_differences=False,
             filename=None, outputs_to_save=None):
-    """(sumse, sumsc, cost): sumse[n][i] = sum over the N paths of output n of model ls[i], sumsc[n][i, j] = sum of the inner
-    products of outputs i and j, cost = N * problem.cost if the problem states one, else the seconds spent in problem.evaluate.
+    """(sumse, sumsc, cost), or (sumse, sumsc, cost, sumsd1, sumsd2) with compute_mlmc_differences: sumse[n][i] = sum over the N paths of output n of model ls[i], sumsc[n][i, j] = sum of the inner
+    products of outputs i and j, cost = N * problem.cost if the problem states one, else the seconds spent in problem.evaluate;
+    sumsd1[n][i][j], sumsd2[n][i][j], i < j: sums of d = (output of ls[i]) - (output of ls[j]) and of inners[n](d, d), 0 elsewhere.
     problem.evaluate(ls, samples) -> Ps[n][i]; sampler(ls) or sampler(ls, count) -> one input per model (default: the same
     standard normal draw for every model); with an MPI communicator the paths are split over its ranks and the sums reduced."""
-    if compute_mlmc_differences or filename is not None or outputs_to_save is not None:
+    if filename is not None or outputs_to_save is not None:
         from .sap import BLUESTError
-        raise BLUESTError("blue_fn: sample files and MLMC difference sums are outside this GPU build (SURVEY.md section 2)")
+        raise BLUESTError("blue_fn: sample files are outside this GPU build (SURVEY.md section 2)")
     comm = comm if comm is not None else _Solo()
     rank, size = comm.Get_rank(), comm.Get_size()
     n_models = len(ls)
@@ -51,6 +55,9 @@ def blue_fn(ls, N, problem, sampler=None, inners=None, comm=None, N1=1, No=1, ve
     todo = int(N) // size + (1 if rank < int(N) % size else 0)
     sumse = [[0] * n_models for _ in range(No)]
     sumsc = [np.zeros((n_models, n_models)) for _ in range(No)]
+    if compute_mlmc_differences:
+        sumsd1 = [[[0] * n_models for _ in range(n_models)] for _ in range(No)]
+        sumsd2 = [[[0] * n_models for _ in range(n_models)] for _ in range(No)]
     spent = 0.0
     while todo > 0:
         count = min(chunk, todo)
@@ -72,9 +79,22 @@ def blue_fn(ls, N, problem, sampler=None, inners=None, comm=None, N1=1, No=1, ve
             for i in range(n_models):
                 for j in range(n_models):
                     sumsc[n][j, i] += np.sum([inners[n](a, b) for a, b in zip(rows[i], rows[j])])
+            if compute_mlmc_differences:
+                for i in range(n_models):
+                    for j in range(i + 1, n_models):
+                        for a, b in zip(rows[i], rows[j]):
+                            sumsd1[n][i][j] = sumsd1[n][i][j] + (a - b)
+                            sumsd2[n][i][j] = sumsd2[n][i][j] + inners[n](a - b, a - b)
         todo -= count
     cost = N * problem.cost if hasattr(problem, "cost") else comm.allreduce(spent)
     for n in range(No):
         sumsc[n] = comm.allreduce(sumsc[n])
         sumse[n] = [comm.allreduce(v) for v in sumse[n]]
+        if compute_mlmc_differences:
+            for i in range(n_models):
+                for j in range(i + 1, n_models):
+                    sumsd1[n][i][j] = comm.allreduce(sumsd1[n][i][j])
+                    sumsd2[n][i][j] = comm.allreduce(sumsd2[n][i][j])
+    if compute_mlmc_differences:
+        return sumse, sumsc, cost, sumsd1, sumsd2
     return sumse, sumsc, cost

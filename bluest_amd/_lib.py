@@ -94,6 +94,7 @@ SIGNATURES = {
     "bluest_mlmc_search": [c_int, c_int, c_int, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "bluest_cov_project": [c_int, c_int, c_vp, c_vp, c_f64, c_f64, c_f64, c_f64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                            c_vp, c_vp],
+    "bluest_pilot_stats": [c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
 
 

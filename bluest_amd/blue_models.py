@@ -8,8 +8,10 @@ groups), their union over the outputs, group costs, one MOSAP on the GPU, `solve
 The projection of the covariances onto the SPD matrices (`project_covariance(s)`, bluest/blue_models.py:348-433) is in scope:
 the eigendecompositions and the whole SPG solve run on the GPU (bluest_cov_project, one workgroup per output).  The
 constructor runs it only when asked (`skip_projection=False`; the default here is True, the reference's is False).
-Out of scope (refused with BLUESTError): estimating covariances or costs by sampling, saving /
-loading model graphs, and -- on this class alone -- the MLMC driver (bluest_amd.mlmc.MLMCMixin provides it).  MFMC (setup_mfmc / solve_mfmc / compute_mfmc_data, the subset search on the
+Refused by this class alone, with BLUESTError, and provided by opt-in mix-ins: estimating covariances, MLMC variances or costs by
+sampling (C=None, NaN entries, costs=None) and saving / loading model graphs (bluest_amd.pilot.PilotMixin, through the hooks
+_init_from_datafile / _init_inputs / _complete_inputs below), and the MLMC driver (bluest_amd.mlmc.MLMCMixin).  Out of scope for
+all of them: sample files, reorder_graph_nodes, complexity_test, variance_test.  MFMC (setup_mfmc / solve_mfmc / compute_mfmc_data, the subset search on the
 GPU) and plain Monte Carlo (solve_mc) are in scope.  An MPI communicator passed
 as `comm` is honoured the way the reference uses it (optimiser, estimators and projection on rank 0 + bcast, samples split
 over the ranks).
@@ -79,17 +81,19 @@ class _SerialComm(object):
     def bcast(self, obj, root=0): return obj
     def allreduce(self, obj, op=None): return obj
     def barrier(self): return None
+    def gather(self, obj, root=0): return [obj]
 
 
 class _Coupling(object):
     """coupling structure of ONE output: the covariance and which pairs of models may share a group"""
 
-    def __init__(self, C, remove_uncorrelated):
+    def __init__(self, C, remove_uncorrelated, unknown_ok=False):
+        """unknown_ok (bluest_amd.pilot.PilotMixin): a NaN entry is a coupled pair whose covariance is still to be estimated"""
         C = np.array(C, dtype=np.float64)
         M = C.shape[0]
         if C.shape != (M, M):
             raise ValueError("covariance must be square")
-        if np.isnan(C).any():
+        if np.isnan(C).any() and not unknown_ok:
             raise BLUESTError("unknown (NaN) covariance entries would have to be estimated by sampling and projected to SPD "
                               "(bluest/blue_models.py:326-433): outside this GPU build -- pass complete covariances")
         never = np.isinf(C)
@@ -115,6 +119,21 @@ class _Coupling(object):
                         nxt.append(j)
             frontier = nxt
         self.component = sorted(seen)
+
+    @classmethod
+    def from_adjacency(cls, A, component):
+        """from a matrix of a model-graph file (bluest/blue_models.py:265-299): 0 = not coupled, inf = coupled and uncorrelated,
+        anything else the covariance of a coupled pair; the component of model 0 is the file's"""
+        self = cls.__new__(cls)
+        A = np.array(A, dtype=np.float64)
+        self.linked = A != 0.0
+        self.cov = np.where(np.isinf(A) | ~self.linked, 0.0, A)
+        self.component = [int(i) for i in component]
+        return self
+
+    def adjacency(self):
+        """the matrix a model-graph file holds for this output"""
+        return np.where(self.linked, np.where(self.cov == 0.0, np.inf, self.cov), 0.0)
 
     def update(self, C_new):
         """the projected covariance on the coupled pairs (bluest/blue_models.py:423-431); which pairs are coupled is unchanged"""
@@ -171,10 +190,9 @@ class BLUEProblem(object):
         self.MOSAP = None
         self.MOSAP_output = None
         if datafile is not None:
-            raise BLUESTError("model-graph files (bluest/blue_models.py:265-299) are outside this GPU build: pass C and costs")
-        if C is None or costs is None:
-            raise BLUESTError("covariances and costs must be given: estimating them by sampling (bluest/blue_models.py:326-346, "
-                              ":435-441) is outside this GPU build")
+            self._init_from_datafile(datafile, costs)
+            return
+        C, costs = self._init_inputs(C, costs)
         Cs = list(C) if isinstance(C, (list, tuple)) else [C]
         if len(Cs) != self.n_outputs or any(np.shape(c) != (self.M, self.M) for c in Cs):
             raise ValueError("need one %d x %d covariance per output" % (self.M, self.M))
@@ -187,7 +205,8 @@ class BLUEProblem(object):
         if self._costs.shape != (self.M,):
             raise ValueError("costs must have one entry per model")
         project = not self.params["skip_projection"]
-        self._coupling = [_Coupling(c, self.params["remove_uncorrelated"] and not project) for c in Cs]
+        self._coupling = [_Coupling(c, self.params["remove_uncorrelated"] and not project, self._unknown_ok) for c in Cs]
+        self._complete_inputs()
         if project:                    # the reference's order (:94-101): project on the user's pattern, then drop uncorrelated pairs
             self.project_covariances()
             for cp in self._coupling:
@@ -198,6 +217,21 @@ class BLUEProblem(object):
                 print("WARNING! Model graph %d is not connected. Connected graph size: %d" % (n, len(cp.component)))
         self.check_costs(warning=True)
         if self.verbose: print("\nBLUE estimator ready.\n")
+
+    # ---- the three places where this class refuses what bluest_amd.pilot.PilotMixin provides ----------------------------------
+    _unknown_ok = False                                        # NaN covariance entries: _Coupling refuses them
+
+    def _init_from_datafile(self, datafile, costs):
+        raise BLUESTError("model-graph files (bluest/blue_models.py:265-299) are outside this GPU build: pass C and costs")
+
+    def _init_inputs(self, C, costs):
+        if C is None or costs is None:
+            raise BLUESTError("covariances and costs must be given: estimating them by sampling (bluest/blue_models.py:326-346, "
+                              ":435-441) is outside this GPU build")
+        return C, costs
+
+    def _complete_inputs(self):
+        """between the coupling graphs and the projection: nothing to do when everything was given"""
 
     # ---- supplied by the user (bluest/blue_models.py:105-119) -----------------------------------------------------------------
     def evaluate(self, ls, samples, N=1):

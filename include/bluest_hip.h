@@ -505,6 +505,30 @@ int bluest_mlmc_search(int nb, int n_out, int flags, double budget, const double
                        const uint32_t *adj, uint32_t *best_mask, uint32_t *best_combo, double *best_obj, int32_t *status,
                        void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Part 10 -- sums over pilot samples for the covariance / MLMC-variance estimates (bluest/blue_models.py:326-346; what
+ * bluest/blue_fn.py:147-167 accumulates with compute_mlmc_differences=True, for scalar outputs and the default inner product
+ * a * b).  values "hd" (host or device pointer, detected with hipPointerGetAttributes): n_out x N x L row-major float64,
+ * values[n][s][i] = output n of model i on joint sample s.  Host outputs, float64:
+ *   sumse  (n_out x L)       sum_s y_i
+ *   sumsc  (n_out x L x L)   sum_s y_i y_j, full and symmetric
+ *   sumsd1 (n_out x L x L)   i < j: sum_s (y_i - y_j), every other entry 0
+ *   sumsd2 (n_out x L x L)   i < j: sum_s (y_i - y_j)^2 from the explicit differences (C_ii + C_jj - 2 C_ij of two nearly equal
+ *                            models has no correct digit left), every other entry 0
+ * sumsd1 and sumsd2 may BOTH be null: no difference sums.  Two launches.  Stage 1, grid (chunk, output): a workgroup stages
+ * BLUEST_PILOT_CHUNK consecutive samples in LDS, every thread owns a fixed set of pairs i <= j and walks the chunk's samples
+ * in ascending order, accumulating in f64 registers; the partial sums go to [output][chunk][pair].  Stage 2 adds the chunks
+ * in ascending order per (output, pair), writes the outputs and mirrors sumsc.  No atomics, and nothing depends on the number of
+ * compute units: THE RESULT IS A FUNCTION OF `values` AND OF BLUEST_PILOT_CHUNK ONLY, bit-identical from run to run and
+ * from machine to machine.  NaN / Inf in `values` propagate.  L outside 1..BLUEST_MAX_MODELS, n_out outside
+ * 1..BLUEST_PILOT_MAX_OUTPUTS, N < 1 (or more than 2^31 - 1 chunks), a null pointer, or exactly one of sumsd1 / sumsd2 null
+ * return BLUEST_ERR_ARG.  Synchronous on `stream`; allocates and frees its own device memory.
+ * --------------------------------------------------------------------------------------------------------- */
+#define BLUEST_PILOT_CHUNK         128   /* samples per workgroup: 64 KB of LDS at L = 64 */
+#define BLUEST_PILOT_MAX_OUTPUTS   1024
+int bluest_pilot_stats(int64_t N, int L, int n_out, const double *values, double *sumse, double *sumsc, double *sumsd1,
+                       double *sumsd2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
