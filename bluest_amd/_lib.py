@@ -95,6 +95,8 @@ SIGNATURES = {
     "bluest_cov_project": [c_int, c_int, c_vp, c_vp, c_f64, c_f64, c_f64, c_f64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                            c_vp, c_vp],
     "bluest_pilot_stats": [c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "bluest_group_sums": [c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp],
+    "bluest_group_sums_slab": [c_i64, c_i64p],
 }
 
 

@@ -10,8 +10,9 @@ the eigendecompositions and the whole SPG solve run on the GPU (bluest_cov_proje
 constructor runs it only when asked (`skip_projection=False`; the default here is True, the reference's is False).
 Refused by this class alone, with BLUESTError, and provided by opt-in mix-ins: estimating covariances, MLMC variances or costs by
 sampling (C=None, NaN entries, costs=None) and saving / loading model graphs (bluest_amd.pilot.PilotMixin, through the hooks
-_init_from_datafile / _init_inputs / _complete_inputs below), and the MLMC driver (bluest_amd.mlmc.MLMCMixin).  Out of scope for
-all of them: sample files, reorder_graph_nodes, complexity_test, variance_test.  MFMC (setup_mfmc / solve_mfmc / compute_mfmc_data, the subset search on the
+_init_from_datafile / _init_inputs / _complete_inputs below), the MLMC driver (bluest_amd.mlmc.MLMCMixin), and batched sampling
+with complexity_test / variance_test (bluest_amd.estimator.SamplingMixin, which replaces _group_sums and solve).  Out of scope for
+all of them: sample files, reorder_graph_nodes.  MFMC (setup_mfmc / solve_mfmc / compute_mfmc_data, the subset search on the
 GPU) and plain Monte Carlo (solve_mc) are in scope.  An MPI communicator passed
 as `comm` is honoured the way the reference uses it (optimiser, estimators and projection on rank 0 + bcast, samples split
 over the ranks).

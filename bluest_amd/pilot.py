@@ -33,15 +33,15 @@ Differences from the reference:
     position among the sampled ones;
   - the arrays passed as mlmc_variances are copied, not written into;
   - the warning about a model dearer than model 0 is printed where BLUEProblem prints it, at the end of the constructor.
-Still refused (BLUESTError): sample files (`samplefile`, `outputs_to_save`), reorder_graph_nodes, complexity_test, variance_test.
+Still refused (BLUESTError): sample files (`samplefile`, `outputs_to_save`) and reorder_graph_nodes; complexity_test and variance_test
+are refused by this mix-in alone and provided by bluest_amd.estimator.SamplingMixin.
 """
 import ctypes
-from inspect import signature
 
 import numpy as np
 
 from . import _lib
-from ._blue_fn import blue_fn, _all_finite
+from ._blue_fn import blue_fn, draw_values
 from .blue_models import BLUEProblem, _Coupling, BLUEST_MAX_MODELS
 from .sap import BLUESTError
 
@@ -150,31 +150,7 @@ class PilotMixin(object):
     def _pilot_values(self, ls, N):
         """this rank's share of N joint samples of the models `ls` as an array [n_outputs, share, len(ls)], drawn with the
         reference's sequence of sampler / evaluate calls (bluest/blue_fn.py:106-129)"""
-        comm = self.get_comm()
-        size, rank = comm.Get_size(), comm.Get_rank()
-        mine = int(N) // size + (1 if rank < int(N) % size else 0)
-        batched = len(signature(self.sampler).parameters) > 1
-        N1 = int(self.params["sample_batch_size"]) if batched else 1
-        out = np.empty((self.n_outputs, mine, len(ls)))
-        done = 0
-        while done < mine:
-            N2 = min(N1, mine - done)
-            while True:
-                samples = self.sampler(ls, N2) if batched else self.sampler(ls)
-                Ps = self.evaluate(ls, samples)
-                if _all_finite(Ps):
-                    break
-                if self.verbose:
-                    print("Warning! Problem evaluation returned inf or NaN value. Resampling...", flush=True)
-            for n in range(self.n_outputs):
-                for i in range(len(ls)):
-                    v = np.asarray(Ps[n][i], dtype=np.float64)
-                    if v.size != N2:
-                        raise BLUESTError("output %d of model %d has %d values for a batch of %d samples: non-scalar outputs need "
-                                          "get_models_inner_products" % (n, ls[i], v.size, N2))
-                    out[n, done:done + N2, i] = v.reshape(N2)
-            done += N2
-        return out
+        return draw_values(self, ls, N)
 
     def _pilot_sums(self, ls, N):
         """per output sumse [L], sumsc [L, L], sumsd1, sumsd2 [L, L] (i < j) over N joint samples of the models `ls`"""

@@ -529,6 +529,44 @@ int bluest_mlmc_search(int nb, int n_out, int flags, double budget, const double
 int bluest_pilot_stats(int64_t N, int L, int n_out, const double *values, double *sumse, double *sumsc, double *sumsd1,
                        double *sumsd2, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Part 11 -- column sums over many ragged segments in one call, and the BLUE estimators they imply (what bluest/blue_fn.py:159-167
+ * accumulates per sample, bluest/blue_models.py:555-571 per group and :963-968 per estimator of a variance test).
+ * A SEGMENT is one (repeat, model group): counts[s] joint samples of sizes[s] models, laid out like Part 10's values,
+ * values[s][n][i][j] = output n of the group's model j on sample i (n_out x counts[s] x sizes[s], row-major float64, 8-byte
+ * aligned).  Each values[s] is a host OR a device pointer, detected per segment; it may be null where counts[s] == 0.  Every
+ * other argument is host memory.  Host segments are copied into one device buffer in slabs of whole chunks (the slab size is
+ * set with bluest_group_sums_slab); device segments are read in place.
+ *   sums (n_out x T, T = sum of sizes)  sums[n][c0(s) + j] = sum_i values[s][n][i][j], c0(s) = sizes[0] + .. + sizes[s-1]
+ *   mu   (R x n_out), with weights (n_out x T) and repeat_of ([S], non-decreasing, 0..R-1):
+ *        mu[r][n] = sum over the segments s of repeat r and their columns j of weights[n][c0(s) + j] * sums[n][c0(s) + j];
+ *        a repeat without segments gives 0.  weights and mu are both given or both null; R and repeat_of are read only with them.
+ * THE ORDER OF EVERY SUMMATION IS FIXED.  Per segment, output and column:
+ *   1. the samples are cut into chunks of BLUEST_GSUM_CHUNK = 128 consecutive samples (the last one may be shorter);
+ *   2. inside a chunk, class k = 0..7 holds the samples 16 k .. 16 k + 15 of the chunk; q_k = the class's values added one by
+ *      one in ascending sample order, starting from +0.0 (an empty class stays +0.0); the chunk's sum is
+ *      ((q_0 + q_1) + (q_2 + q_3)) + ((q_4 + q_5) + (q_6 + q_7));
+ *   3. lane l = 0..63 adds the sums of the chunks l, l + 64, l + 128, ... in ascending order, starting from +0.0; then for
+ *      off = 32, 16, 8, 4, 2, 1 in that order, lane l < off takes p_l = p_l + p_(l + off); the segment's sum is p_0.
+ *   mu[r][n] starts from +0.0 and takes m = fma(weights[n][c], sums[n][c], m) over the columns c of repeat r in ascending order
+ *   (ascending segment, then ascending column of the segment).
+ * So sums of segment s is a function of that segment's values and of BLUEST_GSUM_CHUNK only: not of the device, of the other
+ * segments of the call, of the segment's position, of host or device memory, of the alignment of its base, or of where a slab
+ * ends.  No atomics, nothing sized by the number of compute units.  A segment with counts[s] == 0 gives +0.0.  NaN / Inf propagate.
+ * BLUEST_ERR_ARG: a null counts / sizes / values / sums, a null or misaligned values[s] with counts[s] > 0, S < 1, a size
+ * outside 1..BLUEST_MAX_MODELS, n_out outside 1..BLUEST_GSUM_MAX_OUTPUTS, a negative count, exactly one of weights / mu, with
+ * weights R < 1, a null, decreasing or out-of-range repeat_of, or more than 2^31 - 1 columns or chunks.  Synchronous on `stream`;
+ * allocates and frees its own device memory.
+ * bluest_group_sums_slab(bytes, previous): the staging budget for host segments of the calls that follow (process-wide; default
+ * BLUEST_GSUM_SLAB_BYTES; at least one chunk is always staged); bytes == 0 only reads it; `previous` may be null.
+ * --------------------------------------------------------------------------------------------------------- */
+#define BLUEST_GSUM_CHUNK          128
+#define BLUEST_GSUM_MAX_OUTPUTS    1024
+#define BLUEST_GSUM_SLAB_BYTES     (256LL << 20)
+int bluest_group_sums(int64_t S, int n_out, const int64_t *counts, const int32_t *sizes, const double *const *values,
+                      const double *weights, int R, const int64_t *repeat_of, double *sums, double *mu, void *stream);
+int bluest_group_sums_slab(int64_t bytes, int64_t *previous);
+
 #ifdef __cplusplus
 }
 #endif
