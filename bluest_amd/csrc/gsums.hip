@@ -13,7 +13,7 @@
 //                   weights one thread then walks the group's columns in ascending order with fma.
 // Host segments are copied into one staging buffer slab by slab, every slab a whole number of chunks; the chunks' partial sums
 // all land in one buffer that the single fold reads, so a slab boundary never shows in the result.
-#include "common.hpp"
+#include "staging.hpp"
 
 namespace {
 
@@ -118,14 +118,6 @@ __global__ __launch_bounds__(BLK) void k_gsum_fold(const GFold *__restrict__ fol
         for (int64_t t = f.col0; t < f.col1; t++) m = fma(weights[o * T + t], sums[o * T + t], m);
         mu[f.repeat * n_out + o] = m;
     }
-}
-
-bool on_device(const void *p)
-{
-    hipPointerAttribute_t a;
-    const hipError_t e = hipPointerGetAttributes(&a, p);
-    if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
 struct Piece {              // rows [first, first + rows) of a host segment, staged as [n_out][rows][L] at `at` bytes of its slab

@@ -6,15 +6,8 @@
 //                    sample), then every thread walks the samples in ascending order with its pairs' sums in f64 registers.
 //   k_pilot_fold     grid (pair block, output): adds the chunks in ascending order, writes the outputs, mirrors sumsc.
 //
-// The pair -> thread map.  All threads read the SAME sample row at a time, so what decides LDS bank conflicts is the set of
-// columns a 32-lane half reads with one ds_read_b64: the bank of column i is 2i mod 64, i.e. two columns collide when they differ
-// by 32, and equal columns broadcast.  Pairs are therefore numbered along WRAPPED diagonals, q = d L + i -> {i, (i + d) mod L},
-// d = 0..ceil(L/2)-1 with L entries each, plus half a diagonal d = L/2 when L is even (L (L+1) / 2 pairs in all).  32 consecutive
-// lanes inside one diagonal read 32 consecutive columns i and 32 consecutive columns (i + d) mod L: conflict-free at any L <= 64.
-// At L = 64 every half-wave lies inside one diagonal; at other L a half-wave that straddles two diagonals can see a two-way
-// conflict on a few columns.  A row-major triangle (fixed i, running j) would instead broadcast i and be fine too, but its rows
-// have different lengths, so the half-waves straddle rows almost always; the wrapped diagonals all have length L.
-#include "common.hpp"
+// The pair -> thread map (wrapped diagonals, conflict-free LDS reads) is in staging.hpp.
+#include "staging.hpp"
 
 namespace {
 
@@ -22,17 +15,6 @@ constexpr int BLK = 256;
 constexpr int CHUNK = BLUEST_PILOT_CHUNK;
 constexpr int KMAX = (BLUEST_MAX_MODELS * (BLUEST_MAX_MODELS + 1) / 2 + BLK - 1) / BLK;     // pairs per thread: 9
 static_assert((size_t)CHUNK * BLUEST_MAX_MODELS * sizeof(double) <= 64 * 1024, "the staged chunk must fit the default LDS limit");
-
-__host__ __device__ inline int n_pairs(int L) { return L * ((L + 1) / 2) + ((L & 1) ? 0 : L / 2); }
-
-__device__ __forceinline__ void pair_of(int q, int L, int &lo, int &hi)
-{
-    const int d = q / L, i = q - d * L;
-    int j = i + d;
-    if (j >= L) j -= L;
-    lo = min(i, j);
-    hi = max(i, j);
-}
 
 // part: [output][chunk][slot][pair], slot 0 = sum y_lo y_hi, and with DIFF 1 = sum (y_lo - y_hi), 2 = sum (y_lo - y_hi)^2;
 // parte: [output][chunk][L] = sum y_i
@@ -128,14 +110,6 @@ __global__ __launch_bounds__(BLK) void k_pilot_fold(int64_t nchunks, int L, cons
         for (int64_t c = 0; c < nchunks; c++) e += parte[(o * nchunks + c) * L + q];
         sumse[o * L + q] = e;
     }
-}
-
-bool on_device(const void *p)
-{
-    hipPointerAttribute_t a;
-    const hipError_t e = hipPointerGetAttributes(&a, p);
-    if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
 }  // namespace

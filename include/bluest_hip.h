@@ -567,6 +567,55 @@ int bluest_group_sums(int64_t S, int n_out, const int64_t *counts, const int32_t
                       const double *weights, int R, const int64_t *repeat_of, double *sums, double *mu, void *stream);
 int bluest_group_sums_slab(int64_t bytes, int64_t *previous);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Part 12 -- Parts 10 and 11 for ONE output that is a vector of d components ("field") with a diagonal inner product
+ * <a, b> = sum_c w_c a_c b_c (what bluest/blue_fn.py:147-167 accumulates with the Python inner products of
+ * get_models_inner_products).  One output per call: outputs may differ in d.
+ *
+ * bluest_field_stats.  values "hd" (host or device, detected as in Part 10): N x L x d row-major float64, values[s][i][c] =
+ * component c of model i on joint sample s.  w: host, d weights, finite and >= 0.  Host outputs, float64:
+ *   sumse  (L x d)   sum_s y_i[c]
+ *   sumsc  (L x L)   sum_s sum_c w_c y_i[c] y_j[c], full and symmetric
+ *   sumsd1 (P x d)   P = L (L - 1) / 2, the pairs i < j in row-major order: sum_s (y_i[c] - y_j[c]) from the explicit differences
+ *   sumsd2 (L x L)   i < j: sum_s sum_c w_c (y_i[c] - y_j[c])^2 from the explicit differences, every other entry 0
+ * sumsd1 and sumsd2 may BOTH be null: no difference sums (sumse and sumsc keep their bits).
+ * THE ORDER OF EVERY SUMMATION IS FIXED.  The samples are cut into chunks of BLUEST_PILOT_CHUNK consecutive samples, the
+ * components into tiles of BLUEST_FIELD_TILE = 8 consecutive components (the last of either may be shorter).
+ *   sumse, sumsd1: per (model or pair, component) and chunk, e = e + y_i[c] resp. r = r + (y_i[c] - y_j[c]) over the chunk's
+ *     samples in ascending order from +0.0; the chunks' values are added in ascending order from +0.0.
+ *   sumsc, sumsd2: per pair i <= j, chunk and tile, over the chunk's samples s in ascending order and inside a sample over the
+ *     tile's components c in ascending order, from +0.0:  p = fma(w_c * a, b, p);  dd = a - b;  q = fma(w_c * dd, dd, q)
+ *     with a = y_i[c], b = y_j[c] (w_c * a and w_c * dd rounded to float64).  Per pair and chunk the tiles are joined as the
+ *     chunks of Part 11, step 3: lane l = 0..63 adds the values of the tiles l, l + 64, ... in ascending order from +0.0, then
+ *     for off = 32, 16, 8, 4, 2, 1 lane l < off takes p_l = p_l + p_(l + off); the chunk's value is p_0.  The chunks' values are
+ *     added in ascending order from +0.0.
+ * With d = 1 and w = {1.0} these are the bits of bluest_pilot_stats (n_out = 1).  How many tiles a workgroup takes side by side
+ * (a power of two that follows L and d) and how many samples it stages in LDS at a time shape the launch, not the order.  No
+ * atomics, nothing sized by the number of compute units: the result is a function of `values`, `w`, BLUEST_PILOT_CHUNK and
+ * BLUEST_FIELD_TILE only, the same bits from host or device memory and wherever a slab of staged host data ends.  NaN / Inf in
+ * `values` propagate.  BLUEST_ERR_ARG: L outside 1..BLUEST_MAX_MODELS, d < 1, N < 1, a null values / w / sumse / sumsc,
+ * exactly one of sumsd1 / sumsd2 null, a weight that is not finite or negative, or more than 2^31 - 1 (pair, component) sums
+ * (L (L + 1) / 2 * d) or (chunk, block of tiles) workgroups.  Host input is staged in slabs of whole chunks under the budget of
+ * bluest_group_sums_slab (at least one chunk).  Synchronous on `stream`; allocates and frees its own device memory.
+ *
+ * bluest_field_sums: Part 11 for a field.  Segment s is counts[s] x sizes[s] x d row-major float64 (8-byte aligned), a host OR
+ * a device pointer per segment; it may be null where counts[s] == 0.  Every other argument is host memory.
+ *   sums (T x d, T = sum of sizes)  sums[c0(s) + j][c] = sum_i values[s][i][j][c]
+ *   mu   (R x d), with weights ([T]: the BLUE weight of a (group, model) column is a scalar also for a field, only the inner
+ *        product enters the covariance) and repeat_of ([S], non-decreasing, 0..R-1): mu[r][c] starts from +0.0 and takes
+ *        m = fma(weights[col], sums[col][c], m) over the columns of repeat r in ascending order; a repeat without segments
+ *        gives +0.0.  weights and mu are both given or both null; R and repeat_of are read only with them.
+ * Per (segment, column, component) the samples are added by steps 1-3 of Part 11: with d = 1 these are the bits of
+ * bluest_group_sums (n_out = 1), and the sums of a segment do not depend on the other segments, on its position, on host or
+ * device memory or on where a slab ends.  BLUEST_ERR_ARG as in Part 11 (d < 1 in place of n_out), and more than 2^31 - 1
+ * column-components T d.  Staging budget: bluest_group_sums_slab.  Synchronous on `stream`; allocates and frees its own memory.
+ * --------------------------------------------------------------------------------------------------------- */
+#define BLUEST_FIELD_TILE          8
+int bluest_field_stats(int64_t N, int L, int64_t d, const double *values, const double *w, double *sumse, double *sumsc,
+                       double *sumsd1, double *sumsd2, void *stream);
+int bluest_field_sums(int64_t S, int64_t d, const int64_t *counts, const int32_t *sizes, const double *const *values,
+                      const double *weights, int R, const int64_t *repeat_of, double *sums, double *mu, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
