@@ -49,13 +49,12 @@ def _is_gpu_tensor(v):
     return hasattr(v, "data_ptr") and bool(v.is_cuda)
 
 
-def group_sums(values, weights=None, repeat_of=None, R=None, slab_bytes=SLAB_BYTES):
-    """sums: list over the segments of [n_out, L_s] numpy arrays, sums[s][n, j] = sum_i values[s][n, i, j]; with `weights`
-    ([n_out, sum of L_s]) also mu [R, n_out], mu[r, n] = sum over the segments with repeat_of[s] == r of weights . sums
-    (repeat_of: non-decreasing, default all 0; R: default repeat_of[-1] + 1).  `slab_bytes`: host segments go to the GPU in
-    slabs of whole chunks of at most this size; the result does not depend on it."""
+def _segment_table(values, who):
+    """what the sample-sum entry points take: (the segments as they are passed on -- contiguous float64 numpy arrays and CUDA
+    tensors, kept alive by the caller --, n_out, counts, sizes, the table of their addresses, the stream of the first device
+    tensor's device or None)"""
     if len(values) == 0:
-        raise ValueError("group_sums needs at least one segment")
+        raise ValueError("%s needs at least one segment" % who)
     keep, stream = [], None
     for v in values:
         if hasattr(v, "data_ptr"):
@@ -77,10 +76,19 @@ def group_sums(values, weights=None, repeat_of=None, R=None, slab_bytes=SLAB_BYT
     n_out = int(keep[0].shape[0])
     if any(int(v.shape[0]) != n_out for v in keep):
         raise ValueError("every segment must have the same number of outputs")
-    S = len(keep)
     counts = np.array([int(v.shape[1]) for v in keep], dtype=np.int64)
     sizes = np.array([int(v.shape[2]) for v in keep], dtype=np.int32)
-    ptrs = (ctypes.c_void_p * S)(*[_lib.ptr(v) if v.shape[1] > 0 else None for v in keep])
+    ptrs = (ctypes.c_void_p * len(keep))(*[_lib.ptr(v) if v.shape[1] > 0 else None for v in keep])
+    return keep, n_out, counts, sizes, ptrs, stream
+
+
+def group_sums(values, weights=None, repeat_of=None, R=None, slab_bytes=SLAB_BYTES):
+    """sums: list over the segments of [n_out, L_s] numpy arrays, sums[s][n, j] = sum_i values[s][n, i, j]; with `weights`
+    ([n_out, sum of L_s]) also mu [R, n_out], mu[r, n] = sum over the segments with repeat_of[s] == r of weights . sums
+    (repeat_of: non-decreasing, default all 0; R: default repeat_of[-1] + 1).  `slab_bytes`: host segments go to the GPU in
+    slabs of whole chunks of at most this size; the result does not depend on it."""
+    keep, n_out, counts, sizes, ptrs, stream = _segment_table(values, "group_sums")
+    S = len(keep)
     T = int(sizes.sum())
     sums = np.empty((n_out, T))
     mu = None
@@ -178,6 +186,11 @@ class SamplingMixin(object):
         self._blue_weights_cache = (out, result)
         return result
 
+    def _segments_flushed(self, where, segments):
+        """rank 0, once per flush of _sample_estimators, before the segments are summed: where[i] = (repeat, number of the group
+        in the group list) of segments[i] [n_outputs, N, L], all ranks' shares joined.  A flush never splits a segment.  Nothing is
+        done with them here; bluest_amd.moments.MomentsMixin takes their second moments."""
+
     def _sample_estimators(self, n_rep):
         """mus [n_rep, n_outputs] of n_rep independent estimators of the current allocation: per repeat every selected group is
         drawn in the order of the group list; the segments are summed in group_sums calls of up to SLAB_BYTES of values (counted
@@ -204,8 +217,9 @@ class SamplingMixin(object):
                 first, last = pending[0][0], pending[-1][0]
                 # a flush may begin or end inside a repeat: every segment brings the weights of its own group
                 weights = np.concatenate([W[:, first_col[gi]:first_col[gi] + width[gi]] for _, gi, _ in pending], axis=1)
-                _, part = group_sums([self._joined([share[i] for share in shares]) for i in range(len(pending))], weights=weights,
-                                     repeat_of=[r - first for r, _, _ in pending], R=last - first + 1)
+                joined = [self._joined([share[i] for share in shares]) for i in range(len(pending))]
+                self._segments_flushed([(r, int(chosen[gi])) for r, gi, _ in pending], joined)
+                _, part = group_sums(joined, weights=weights, repeat_of=[r - first for r, _, _ in pending], R=last - first + 1)
                 mus[first:last + 1] += part
             del pending[:]
 

@@ -616,6 +616,32 @@ int bluest_field_stats(int64_t N, int L, int64_t d, const double *values, const 
 int bluest_field_sums(int64_t S, int64_t d, const int64_t *counts, const int32_t *sizes, const double *const *values,
                       const double *weights, int R, const int64_t *repeat_of, double *sums, double *mu, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Part 13 -- first and second moments of many ragged segments in one call: what the sample covariance of every drawn model
+ * group is made of.  Segments, counts, sizes, values[s] (host OR device per segment, 8-byte aligned, null allowed where
+ * counts[s] == 0) and the staging budget (bluest_group_sums_slab) are exactly those of Part 11.  Host outputs, float64.
+ * THE SHIFT.  Per (segment s, output n) every value enters as d_ij = values[s][n][i][j] - a_j with a_j = values[s][n][0][j], the
+ * segment's first sample: one rounding.  The sums below keep their meaning when |mean| >> std, in one pass over the data.
+ *   first  (n_out x T, T = sum of sizes)   first[n][c0(s) + j] = sum_i d_ij, c0(s) as in Part 11
+ *   second (n_out x P, P = sum of sizes[s] (sizes[s] + 1) / 2): per segment the upper triangle j <= k, packed row-major (L = sizes[s]):
+ *          second[n][p0(s) + j L - j (j - 1) / 2 + (k - j)] = sum_i d_ij d_ik, p0(s) = the triangle sizes of the segments before s.
+ * The unbiased sample covariance of segment s is (second - first first^T / N) / (N - 1), N = counts[s]: the shift drops out.
+ * THE ORDER OF EVERY OPERATION IS FIXED.
+ *   first:  steps 1-3 of Part 11 applied to d.
+ *   second: the same three steps per pair j <= k; inside a class of step 2 the accumulation is q = fma(d_ij, d_ik, q) over the
+ *           class's samples in ascending order from +0.0 (one rounding per term); the classes join as
+ *           ((q_0 + q_1) + (q_2 + q_3)) + ((q_4 + q_5) + (q_6 + q_7)); the chunks fold as in step 3.
+ * So the results of segment s are a function of that segment's values and of BLUEST_GSUM_CHUNK only: not of the device, of the
+ * other segments of the call, of the segment's position, of host or device memory, of the alignment of its base, or of where a
+ * slab ends (the first samples of the host segments travel apart from the slabs).  No atomics, nothing sized by the number of
+ * compute units, no matrix instructions.  counts[s] == 0 and counts[s] == 1 give +0.0 everywhere (for one sample d is exactly
+ * 0).  NaN / Inf propagate (Inf - Inf is NaN).  BLUEST_ERR_ARG as in Part 11 (without the weights), and for a null first or
+ * second, and for more than 2^31 - 1 packed pairs P.  Without a device BLUEST_ERR_NOGPU: there is no CPU path.  Synchronous on
+ * `stream`; allocates and frees its own device memory.
+ * --------------------------------------------------------------------------------------------------------- */
+int bluest_group_moments(int64_t S, int n_out, const int64_t *counts, const int32_t *sizes, const double *const *values,
+                         double *first, double *second, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
