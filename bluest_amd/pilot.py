@@ -152,6 +152,11 @@ class PilotMixin(object):
         reference's sequence of sampler / evaluate calls (bluest/blue_fn.py:106-129)"""
         return draw_values(self, ls, N)
 
+    def _pilot_gathered(self, ls, values):
+        """rank 0: the values of all ranks [n_outputs, N, len(ls)] on their way to pilot_statistics.  Nothing to do here;
+        bluest_amd.pilot_errors.PilotErrorsMixin keeps them"""
+        return values
+
     def _pilot_sums(self, ls, N):
         """per output sumse [L], sumsc [L, L], sumsd1, sumsd2 [L, L] (i < j) over N joint samples of the models `ls`"""
         if type(self).get_models_inner_products is not BLUEProblem.get_models_inner_products:
@@ -163,7 +168,7 @@ class PilotMixin(object):
         parts = comm.gather(self._pilot_values(ls, N), root=0)
         sums = None
         if comm.Get_rank() == 0:                                        # the kernel runs on one rank, as the projection does
-            values = parts[0] if len(parts) == 1 else np.concatenate(parts, axis=1)
+            values = self._pilot_gathered(ls, parts[0] if len(parts) == 1 else np.concatenate(parts, axis=1))
             sums = pilot_statistics(values, differences=True)
         return comm.bcast(sums, root=0)
 

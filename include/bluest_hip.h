@@ -642,6 +642,43 @@ int bluest_field_sums(int64_t S, int64_t d, const int64_t *counts, const int32_t
 int bluest_group_moments(int64_t S, int n_out, const int64_t *counts, const int32_t *sizes, const double *const *values,
                          double *first, double *second, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Part 14 -- sums over pilot samples up to the fourth order: what the standard errors of Part 10's covariance and
+ * MLMC-variance estimates are made of (the reference has no counterpart: its pilot size is a guess nothing checks).
+ * values: exactly Part 10's array, "hd" (host or device, detected as there), n_out x N x L row-major float64.
+ * THE SHIFT.  shift: a HOST array n_out x L, or null = the first sample, a_i = values[n][0][i].  Every value enters as
+ * d_i = y_i - a_i (one rounding), so the sums keep their meaning when |mean| >> std; an explicit shift lets a host array go
+ * in slabs that share the shift of the first.  Host outputs, float64:
+ *   first (n_out x L)           sum_s d_i
+ *   s11   (n_out x L x L)       sum_s d_i d_j, full and symmetric
+ *   s21   (n_out x L x L)       s21[i][j] = sum_s d_i^2 d_j, full and NOT symmetric; the diagonal holds sum_s d_i^3
+ *   s22   (n_out x L x L)       sum_s d_i^2 d_j^2, full and symmetric; the diagonal holds sum_s d_i^4
+ *   tpow  (n_out x 4 x L x L)   may be null.  Slot k - 1 (k = 1..4) holds sum_s t^k at i < j, every other entry +0.0, with
+ *                               t = (y_i - y_j) - (a_i - a_j): each inner subtraction rounded once, then the outer one.  t comes
+ *                               from the explicit differences for the reason Part 10 gives.  With tpow null the other outputs
+ *                               keep their bits.
+ * THE ORDER OF EVERY OPERATION IS FIXED.  The samples are cut into chunks of BLUEST_PILOT_CHUNK consecutive samples (the last
+ * may be shorter).  Inside a chunk the samples go in ascending order, every sum starting from +0.0:
+ *   first: e = e + d_i.
+ *   per pair lo <= hi, with a = d_lo, b = d_hi and p = a * b rounded to float64:
+ *     S11 = fma(a, b, S11);  S21[lo][hi] = fma(a, p, S21[lo][hi]);  S21[hi][lo] = fma(b, p, S21[hi][lo]);  S22 = fma(p, p, S22);
+ *     on the diagonal the two S21 updates are the same value, written once.
+ *   per pair lo < hi, with t as above and q = t * t rounded to float64:
+ *     T1 = T1 + t;  T2 = fma(t, t, T2);  T3 = fma(q, t, T3);  T4 = fma(q, q, T4).
+ * The chunks' values are then added in ascending order from +0.0.  So the result is a function of `values`, `shift` and
+ * BLUEST_PILOT_CHUNK only: the same bits from host or device memory, from run to run and from machine to machine, for one
+ * output alone or inside a batch.  No atomics, nothing sized by the number of compute units, no matrix instructions.  N == 1
+ * with a null shift gives +0.0 everywhere.  NaN / Inf propagate.  Two launches as in Part 10 (partial sums per (chunk, output),
+ * then the fold over the chunks).  The staged chunk fills the default 64 KB of LDS at L = 64, so the shift never lives there:
+ * without tpow it is subtracted while the chunk is staged; with tpow the chunk is staged as it lies (t needs the values
+ * themselves), a thread holds a_lo and a_hi of its pairs in registers, and all eight sums come from the same two LDS reads.
+ * BLUEST_ERR_ARG, returned before anything is written: L outside 1..BLUEST_MAX_MODELS, n_out outside
+ * 1..BLUEST_PILOT_MAX_OUTPUTS, N < 1, more than 2^31 - 1 chunks, or a null values / first / s11 / s21 / s22.  Without a device
+ * BLUEST_ERR_NOGPU: there is no CPU path.  Synchronous on `stream`; allocates and frees its own device memory.
+ * --------------------------------------------------------------------------------------------------------- */
+int bluest_pilot_moments4(int64_t N, int L, int n_out, const double *values, const double *shift, double *first, double *s11,
+                          double *s21, double *s22, double *tpow, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
