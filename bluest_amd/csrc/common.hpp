@@ -64,6 +64,17 @@ __device__ __forceinline__ double wave_min(double x)
     for (int off = 32; off > 0; off >>= 1) x = fmin(x, __shfl_xor(x, off, WAVE));
     return x;
 }
+// The binary exponent e of x (x = f 2^e with 0.5 <= f < 1), and 0 for zero, inf and NaN.  With x the largest |entry| of a block,
+// ldexp(a, -e) brings the block to ordinary size exactly, and since pinv(s A) = pinv(A) / s, ldexp(r, -e) carries a pseudo-inverse
+// of the scaled block back: the Jacobi pseudo-inverses (mirrors.hip, plan.hip) form squares and products of entries, which
+// overflow from 2^512 and vanish below 2^-537 unscaled.  A block whose largest entry lies within 2^-256 .. 2^256 is left as it is
+// (e = 0: its squares are safe, and its result keeps the bits it had before the scaling existed).
+__device__ __forceinline__ int pow2_exponent(double x)
+{
+    int e = 0;
+    if (x > 0.0 && x < INFINITY) (void)frexp(x, &e);
+    return (e > 256 || e < -256) ? e : 0;
+}
 __device__ __forceinline__ long long wave_sum_ll(long long x)
 {
 #pragma unroll

@@ -236,7 +236,21 @@ __global__ __launch_bounds__(64) void k_group_pinv(const double *__restrict__ C,
             const int64_t a = (int64_t)gi[j], b = (int64_t)gi[l];
             A[j * K + l] = 0.5 * (C[a * N + b] + C[b * N + a]);
         }
-    sym_pinv_jacobi<K>(A, V, out + i * (int64_t)K * K);
+    // A block whose largest entry lies outside 2^-256 .. 2^256 is scaled by a power of two to ordinary size and its result scaled
+    // back (pow2_exponent, common.hpp): the sums of squares of sym_pinv_jacobi's stopping test would otherwise be inf (entries from
+    // 2^512) or 0 (below 2^-537), either of which ends the sweeps at once and returns diag(1 / a_ii) as if converged.
+    double amax = 0.0;
+#pragma unroll
+    for (int t = 0; t < K * K; t++) amax = fmax(amax, fabs(A[t]));
+    const int e = pow2_exponent(amax);
+    if (e != 0) {
+#pragma unroll
+        for (int t = 0; t < K * K; t++) A[t] = ldexp(A[t], -e);
+    }
+    double *o = out + i * (int64_t)K * K;
+    sym_pinv_jacobi<K>(A, V, o);
+    if (e != 0)
+        for (int t = 0; t < K * K; t++) o[t] = ldexp(o[t], -e);
 }
 
 // Groups of 17..32 models: two K x K arrays per thread no longer fit the register file, so one wavefront owns one group and

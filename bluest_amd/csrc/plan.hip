@@ -395,6 +395,15 @@ __global__ __launch_bounds__(64) void k_pinv_from_record(int N, int n_out, const
                     A[lane * LD + j] = in ? 0.5 * (r[lane * N + j] + r[j * N + lane]) + (lane == j ? delta : 0.0) : 0.0;
                     Q[lane * LD + j] = lane == j ? 1.0 : 0.0;
                 }
+            // scaled to ordinary size by a power of two where max|a| lies outside 2^-256 .. 2^256 (pow2_exponent, common.hpp):
+            // the rotation threshold of jacobi_pinv_lds is a product of two entries, inf from 2^512 on (nothing rotates) and 0
+            // below 2^-537 (nothing is skipped)
+            double rmax = 0.0;
+            if (lane < N)
+                for (int j = 0; j < N; j++) rmax = fmax(rmax, fabs(A[lane * LD + j]));
+            const int sh = pow2_exponent(wave_max(rmax));
+            if (lane < N)
+                for (int j = 0; j < N; j++) A[lane * LD + j] = ldexp(A[lane * LD + j], -sh);
             wave_lds_sync();
             jacobi_pinv_lds(A, Q, N, LD, lane);
             const double w = lane < N ? A[lane * LD + lane] : 0.0;
@@ -405,13 +414,13 @@ __global__ __launch_bounds__(64) void k_pinv_from_record(int N, int n_out, const
             if (pass == 0) {
                 double acc = 0.0;
                 for (int ee = 0; ee < N; ee++) acc += Q[t * LD + ee] * A[ee * LD + ee] * Q[t * LD + ee];
-                V = acc;
+                V = ldexp(acc, -sh);
             }
             if (pass == npass - 1) {                           // row 0 of pinv(Phi): zero when model 0 is outside the support
                 double acc = 0.0;
                 if (lane < N && (mask2 & 1ull))
                     for (int ee = 0; ee < N; ee++) acc += Q[0 * LD + ee] * A[ee * LD + ee] * Q[lane * LD + ee];
-                vmine = acc;
+                vmine = ldexp(acc, -sh);
             }
             wave_lds_sync();
         }
