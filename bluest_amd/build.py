@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["runtime.hip", "mirrors.hip", "plan.hip", "spg.hip", "intproj.hip", "xchg.hip", "newton.hip", "matfree.hip", "mfmc.hip", "mlmc.hip", "covproj.hip", "pilot.hip", "gsums.hip", "fields.hip", "moments.hip", "pilot4.hip", "wave_probe.hip"]     # translation units of libbluest_hip.so
+SOURCES = ["runtime.hip", "mirrors.hip", "plan.hip", "spg.hip", "intproj.hip", "xchg.hip", "newton.hip", "matfree.hip", "mfmc.hip", "mlmc.hip", "covproj.hip", "pilot.hip", "gsums.hip", "fields.hip", "moments.hip", "pilot4.hip", "field_moments.hip", "wave_probe.hip"]     # translation units of libbluest_hip.so
 HEADERS = ["common.hpp", "solve.hpp", "plan.hpp", "spg_state.hpp", "jacobi.hpp", "subset_search.hpp", "staging.hpp"]
 OBJDIR = os.path.join(CSRC, "_build")
 HDR = os.path.join(ROOT, "include", "bluest_hip.h")

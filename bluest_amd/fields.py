@@ -87,13 +87,12 @@ def field_statistics(values, w, differences=True):
     return sumse, sumsc, sumsd1, sumsd2
 
 
-def field_group_sums(values, weights=None, repeat_of=None, R=None, slab_bytes=SLAB_BYTES):
-    """sums: list over the segments of [L_s, d] numpy arrays, sums[s][j, c] = sum_i values[s][i, j, c]; with `weights`
-    ([sum of L_s], one scalar per column) also mu [R, d], mu[r] = sum over the segments with repeat_of[s] == r of
-    weights . sums (repeat_of: non-decreasing, default all 0; R: default repeat_of[-1] + 1).  `slab_bytes`: host segments go to
-    the GPU in slabs of whole chunks of at most this size; the result does not depend on it."""
+def _field_segment_table(values, who):
+    """what the field entry points over ragged segments take: (the segments [N_s, L_s, d] as they are passed on -- contiguous
+    float64 numpy arrays and CUDA tensors, kept alive by the caller --, d, counts, sizes, the table of their addresses, the stream
+    of the first device tensor's device or None)"""
     if len(values) == 0:
-        raise ValueError("field_group_sums needs at least one segment")
+        raise ValueError("%s needs at least one segment" % who)
     keep = [_segment(v, "every segment") for v in values]
     d = int(keep[0].shape[2])
     if any(int(v.shape[2]) != d for v in keep):
@@ -103,10 +102,19 @@ def field_group_sums(values, weights=None, repeat_of=None, R=None, slab_bytes=SL
         if hasattr(v, "data_ptr"):
             stream = _stream_of(v)
             break
-    S = len(keep)
     counts = np.array([int(v.shape[0]) for v in keep], dtype=np.int64)
     sizes = np.array([int(v.shape[1]) for v in keep], dtype=np.int32)
-    ptrs = (ctypes.c_void_p * S)(*[_lib.ptr(v) if v.shape[0] > 0 else None for v in keep])
+    ptrs = (ctypes.c_void_p * len(keep))(*[_lib.ptr(v) if v.shape[0] > 0 else None for v in keep])
+    return keep, d, counts, sizes, ptrs, stream
+
+
+def field_group_sums(values, weights=None, repeat_of=None, R=None, slab_bytes=SLAB_BYTES):
+    """sums: list over the segments of [L_s, d] numpy arrays, sums[s][j, c] = sum_i values[s][i, j, c]; with `weights`
+    ([sum of L_s], one scalar per column) also mu [R, d], mu[r] = sum over the segments with repeat_of[s] == r of
+    weights . sums (repeat_of: non-decreasing, default all 0; R: default repeat_of[-1] + 1).  `slab_bytes`: host segments go to
+    the GPU in slabs of whole chunks of at most this size; the result does not depend on it."""
+    keep, d, counts, sizes, ptrs, stream = _field_segment_table(values, "field_group_sums")
+    S = len(keep)
     T = int(sizes.sum())
     sums = np.empty((T, d))
     mu = None
@@ -278,6 +286,11 @@ class FieldOutputsMixin(object):
         return self.get_comm().bcast(sums, root=0)
 
     # ---- whole estimators (bluest_amd.estimator.SamplingMixin) ----------------------------------------------------------------------
+    def _field_segments_flushed(self, where, n, segments):
+        """rank 0, once per output and flush of _sample_estimators, before the segments are summed: where[i] = (repeat, number of
+        the group in the group list) of segments[i] [N, L, d_n] of output n, all ranks' shares joined.  A flush never splits a
+        segment.  Nothing is done with them here; bluest_amd.field_errors.FieldErrorsMixin takes their weighted moments."""
+
     def _sample_estimators(self, n_rep):
         """per output mus [n_rep, d_n] of n_rep independent estimators of the current allocation, drawn and flushed as
         SamplingMixin._sample_estimators does, with one field_group_sums call per output and flush"""
@@ -307,9 +320,11 @@ class FieldOutputsMixin(object):
                 first, last = pending[0][0], pending[-1][0]
                 # a flush may begin or end inside a repeat: every segment brings the weights of its own group
                 cols = np.concatenate([np.arange(first_col[gi], first_col[gi] + width[gi]) for _, gi, _ in pending])
+                where = [(r, int(chosen[gi])) for r, gi, _ in pending]
                 for n in range(self.n_outputs):
-                    _, part = field_group_sums([_joined([share[i][n] for share in shares]) for i in range(len(pending))],
-                                               weights=W[n, cols], repeat_of=[r - first for r, _, _ in pending], R=last - first + 1)
+                    joined = [_joined([share[i][n] for share in shares]) for i in range(len(pending))]
+                    self._field_segments_flushed(where, n, joined)
+                    _, part = field_group_sums(joined, weights=W[n, cols], repeat_of=[r - first for r, _, _ in pending], R=last - first + 1)
                     mus[n][first:last + 1] += part
             del pending[:]
 

@@ -679,6 +679,43 @@ int bluest_group_moments(int64_t S, int n_out, const int64_t *counts, const int3
 int bluest_pilot_moments4(int64_t N, int L, int n_out, const double *values, const double *shift, double *first, double *s11,
                           double *s21, double *s22, double *tpow, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Part 15 -- sums and sums of squares of a weighted combination of a field's models, per component, over many ragged segments
+ * in one call: what the sampled variance of every component of a BLUE field estimate is made of (the reference has no
+ * counterpart).  Segments, counts, sizes, values[s] (counts[s] x sizes[s] x d row-major float64, a host OR a device pointer per
+ * segment, 8-byte aligned, null allowed where counts[s] == 0) and the staging budget (bluest_group_sums_slab) are exactly those of
+ * bluest_field_sums.  coef: host, T = sum of sizes entries, one finite scalar per column (the BLUE weight of a (group, model)
+ * column is a scalar also for a field); 0 is allowed.  Host outputs, float64, both S x d.
+ * THE SHIFT.  Every value enters as d_ij[c] = values[s][i][j][c] - values[s][0][j][c], the segment's first sample subtracted: one
+ * rounding, as in Part 13.  A mean far above the standard deviation costs no digit, in one pass over the data.
+ *   z_i[c]      the combination of sample i: starts from +0.0 and takes z = fma(coef[c0(s) + j], d_ij[c], z) over the columns
+ *               j = 0 .. sizes[s] - 1 of the segment in ascending order, c0(s) as in Part 11
+ *   zsum[s][c] = sum_i z_i[c]
+ *   zsq[s][c]  = sum_i z_i[c]^2
+ * The unbiased variance of z over segment s is (zsq - zsum^2 / N) / (N - 1), N = counts[s]: the shift drops out.
+ * THE ORDER OF EVERY OPERATION IS FIXED.  Per (segment, component) the samples are added by steps 1-3 of Part 11: chunks of
+ * BLUEST_GSUM_CHUNK consecutive samples; inside a chunk eight classes of sixteen consecutive samples, each from +0.0 in ascending
+ * order with q = q + z for zsum and q = fma(z, z, q) for zsq (one rounding per term); the classes join as
+ * ((q_0 + q_1) + (q_2 + q_3)) + ((q_4 + q_5) + (q_6 + q_7)); lane l = 0..63 adds the chunks l, l + 64, ... in ascending order from
+ * +0.0, and for off = 32, 16, 8, 4, 2, 1 lane l < off takes p_l = p_l + p_(l + off); the result is p_0.
+ * So the results of segment s are a function of that segment's values, of its coefficients and of BLUEST_GSUM_CHUNK only: not of
+ * the device, of the other segments of the call, of the segment's position, of host or device memory, of the alignment of its
+ * base, of where a slab ends (the first samples of the host segments travel apart from the slabs), or of the launch shape (which
+ * follows sizes[s] and d: a thread per component reading memory along c where d >= 64, sub-blocks of samples staged in LDS
+ * below).  No atomics, nothing sized by the number of compute units, no matrix instructions.
+ * TWO ANCHORS.  For a segment with sizes[s] == 1 and coef == 1.0, z = d, so for d <= BLUEST_MAX_MODELS zsum[s] is bit for bit
+ * `first` of bluest_group_moments on the same counts[s] x d values read as [n_out = 1, N = counts[s], L = d], and zsq[s] is bit
+ * for bit the diagonal of its `second`.
+ * counts[s] == 0 and counts[s] == 1 give +0.0 everywhere (for one sample d is exactly 0).  NaN / Inf propagate (Inf - Inf is
+ * NaN).  BLUEST_ERR_ARG, returned before anything is written: the cases of bluest_field_sums (S < 1, d < 1, a null counts / sizes
+ * / values, a size outside 1..BLUEST_MAX_MODELS, a negative count, a null or misaligned values[s] with counts[s] > 0, more than
+ * 2^31 - 1 columns, chunks or column-components T d), a null coef, zsum or zsq, a coefficient that is not finite, more than
+ * 2^31 - 1 values S d, or more than 2^31 - 1 (chunk, block of 64 components, class) workgroups.  Without a device BLUEST_ERR_NOGPU:
+ * there is no CPU path.  Synchronous on `stream`; allocates and frees its own device memory.
+ * --------------------------------------------------------------------------------------------------------- */
+int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t *counts, const int32_t *sizes, const double *const *values,
+                                  const double *coef, double *zsum, double *zsq, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
