@@ -13,6 +13,10 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["runtime.hip", "mirrors.hip", "plan.hip", "spg.hip", "intproj.hip", "xchg.hip", "newton.hip", "matfree.hip", "mfmc.hip", "mlmc.hip", "covproj.hip", "pilot.hip", "gsums.hip", "fields.hip", "moments.hip", "pilot4.hip", "field_moments.hip", "wave_probe.hip"]     # translation units of libbluest_hip.so
 HEADERS = ["common.hpp", "solve.hpp", "plan.hpp", "spg_state.hpp", "jacobi.hpp", "subset_search.hpp", "staging.hpp"]
+# flags of single units.  plan.hip: the first 14 dwords of a kernel's arguments arrive in scalar registers with the wavefront (kernarg
+# preload; the step kernels' argument order is made for it, csrc/plan.hip).  BLUEST_EXTRA_HIPCC_FLAGS follows them on the command
+# line, so "-mllvm -amdgpu-kernarg-preload-count=0" there builds the same sources without it.
+SOURCE_FLAGS = {"plan.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"]}
 OBJDIR = os.path.join(CSRC, "_build")
 HDR = os.path.join(ROOT, "include", "bluest_hip.h")
 LIB = os.path.join(HERE, "libbluest_hip.so")
@@ -30,21 +34,26 @@ def _inputs():
     return [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [HDR]
 
 
-STAMP = os.path.join(OBJDIR, "hipcc_flags.txt")      # the extra flags the library was built with: an experiment build is never "current"
+STAMP = os.path.join(OBJDIR, "hipcc_flags.txt")      # the extra and per-unit flags the library was built with: an experiment build is never "current"
 
 
 def _extra_flags():
     return os.environ.get("BLUEST_EXTRA_HIPCC_FLAGS", "").split()
 
 
+def _stamp_text():
+    """what the stamp holds: the extra flags, then one line per unit that has flags of its own (SOURCE_FLAGS)"""
+    return "\n".join([" ".join(_extra_flags())] + ["%s: %s" % (name, " ".join(SOURCE_FLAGS[name])) for name in sorted(SOURCE_FLAGS)])
+
+
 def up_to_date():
     if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(f) for f in _inputs()):
         return False
     try:
-        built_with = open(STAMP).read().split()
+        built_with = open(STAMP).read()
     except OSError:
-        built_with = []
-    return built_with == _extra_flags()
+        built_with = None
+    return built_with == _stamp_text()
 
 
 SHIM_SRC = os.path.join(HERE, "csrc", "cmisc_shim.cpp")
@@ -78,11 +87,11 @@ def build(force=False, verbose=False):
     from concurrent.futures import ThreadPoolExecutor
     os.makedirs(OBJDIR, exist_ok=True)
     flags = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-pthread", "-I" + os.path.join(ROOT, "include"),
-             "-I" + CSRC] + _extra_flags()
+             "-I" + CSRC]
 
     def compile_one(name):
         obj = os.path.join(OBJDIR, os.path.splitext(name)[0] + ".o")
-        cmd = [hipcc()] + flags + ["-c", os.path.join(CSRC, name), "-o", obj]
+        cmd = [hipcc()] + flags + SOURCE_FLAGS.get(name, []) + _extra_flags() + ["-c", os.path.join(CSRC, name), "-o", obj]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
@@ -95,7 +104,7 @@ def build(force=False, verbose=False):
         print(" ".join(cmd))
     subprocess.check_call(cmd)
     with open(STAMP, "w") as f:
-        f.write(" ".join(_extra_flags()))
+        f.write(_stamp_text())
     build_shim(force=True, verbose=verbose)
     return LIB
 

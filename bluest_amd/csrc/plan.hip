@@ -55,16 +55,16 @@ template <> __device__ __forceinline__ int4 load_cols4<uint16_t>(const uint16_t 
     return make_int4((int)(w.x & 0xffffu), (int)(w.x >> 16), (int)(w.y & 0xffffu), (int)(w.y >> 16));
 }
 // Phi pass: one wavefront per chunk of CH = 256*iters entries; lane l owns entries [4l, 4l+4) of each 256-block.
-// Prologue of both chunk kernels: the arguments are pinned into one batch (kernarg_now), the gate word costs one more scalar
-// wait, and the slot of the chunk's partial -- needed by the final store only -- is loaded without a branch (a plan without a slot
-// table reads a dummy word and keeps the chunk number), so no wait stands between the launch and the first streaming load.
+// Prologue of both chunk kernels: what the stream needs arrives in scalar registers with the wavefront (see "Arguments" below), the
+// gate of a launch that has one costs two scalar round trips (pointer, word), and the slot of the chunk's partial -- needed behind
+// the loop only -- is a scalar load without a branch (a plan without a slot table reads a dummy word and keeps the chunk
+// number), so no wait stands between the launch and the first streaming load.
 // Tail: every workgroup is whole wavefronts and the early exits are wave-uniform, so all 64 lanes reach the reductions, which
 // run on the VALU (wave_sum_dpp / wave_max_dpp, common.hpp).
 // The slot word of a plan without a slot table is a dummy read of the first four bytes of the column stream (always there: the
 // plan has at least one chunk); its value is discarded, only the absence of a branch around the load matters.
-// What the compiler makes of this prologue and of the addressing below is recorded in profiles/r07_isa_counts.txt (tools/isa_counts.py):
+// What the compiler makes of this prologue and of the addressing below is recorded in profiles/r09_isa_counts.txt (tools/isa_counts.py):
 // re-check it there after a toolchain update.
-__device__ __forceinline__ bool phi_gate_closed(const int32_t *gate) { return gate && uniform_word(gate) == 0; }
 // Addressing of both chunk kernels: a wavefront's chunk, its output block and every base of vals / cols / m / partial are
 // wave-uniform and live on the SALU; a lane adds one 32-bit byte offset per stream (the loads and the store take the scalar base
 // plus that offset).  What makes 32 bits enough: bluest_plan_finalize refuses plans of more than 0x7fffffff0 entries, so a chunk
@@ -77,28 +77,35 @@ template <int WPB> __device__ __forceinline__ uint32_t phi_wave_chunk()
     if constexpr (WPB == 1) return blockIdx.x;
     else return blockIdx.x * WPB + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 }
+// Arguments of both chunk kernels.  The first 14 dwords of a kernel's argument list arrive in scalar registers with the wavefront
+// (kernarg preload, the -mllvm option bluest_amd/build.py gives this unit), so everything the common path needs in front of its first
+// streaming load stands there, as plain pointers and 32-bit scalars: vals, cols, m, pslot, iters, the chunk count, n_out, n_cand
+// and a flags word (PHI_HAS_GATE: the gate pointer is loaded, one scalar round trip, only by a launch that has one).  The others
+// are first needed by the store: their scalar loads are issued in front of the stream and waited for behind the issue of its first
+// loads (phi_late_args, called in the loop), so the round trip to the argument segment runs under the one to the stream.
+constexpr uint32_t PHI_HAS_GATE = 1u;
+template <class... A> __device__ __forceinline__ void phi_late_args(const A &...a) { kernarg_now(a...); }
 template <int WPB, typename COLT>
 __global__ __launch_bounds__(64 * WPB) void k_phi_chunks(const double *__restrict__ vals, const COLT *__restrict__ cols,
-                                                    int iters, int64_t n_chunks, const double *__restrict__ m,
-                                                    int64_t m_stride, int n_cand, double2 *__restrict__ partial,
-                                                    const int32_t *__restrict__ pslot, int64_t pstride,
-                                                    const int32_t *__restrict__ gate)
+                                                    const double *__restrict__ m, const int32_t *__restrict__ pslot,
+                                                    int iters, uint32_t n_chunks, int n_out, int n_cand, uint32_t flags,
+                                                    const int32_t *__restrict__ gate, int64_t m_stride, int64_t pstride,
+                                                    int slots_per_output, double2 *__restrict__ partial)
 {
-    kernarg_now(vals, cols, iters, n_chunks, m, m_stride, n_cand, partial, pslot, pstride, gate);
-    const bool closed = phi_gate_closed(gate);      // device-side predication (SPG line-search slots)
+    (void)n_out; (void)slots_per_output;      // (one argument list for both chunk kernels)
     const uint32_t chunk = phi_wave_chunk<WPB>();
     const uint32_t lane = threadIdx.x & 63;
-    if (closed) return;
-    if (chunk >= (uint32_t)n_chunks) return;
+    if (flags & PHI_HAS_GATE) { if (uniform_word(gate) == 0) return; }      // device-side predication (SPG line-search slots)
+    if (chunk >= n_chunks) return;
     // where the fold expects this chunk's partial (in flight until the store; both early exits are scalar branches without a
     // wait of their own, so the load loses nothing behind them)
-    const int32_t slot_ld = *(pslot ? pslot + chunk : reinterpret_cast<const int32_t *>(cols));
+    const int32_t slot_ld = uniform_word(pslot ? pslot + chunk : reinterpret_cast<const int32_t *>(cols));
     const uint64_t base = (uint64_t)chunk * ((uint32_t)iters * 256u);      // entries in front of this chunk
     const char *vb = reinterpret_cast<const char *>(vals + base);
     const char *cb = reinterpret_cast<const char *>(cols + base);
     const double *mc = m;
-    char *pc = reinterpret_cast<char *>(partial);
-    for (int c = 0; c < n_cand; c++, mc += m_stride, pc += pstride * (int64_t)sizeof(double2)) {
+    int64_t pdone = 0;      // candidates' partials in front of this one, in bytes
+    for (int c = 0; c < n_cand; c++) {
         double s = 0.0, amax = 0.0;
         uint32_t vo = lane * 32u, co = lane * (uint32_t)(4 * sizeof(COLT));
         int it = 0;
@@ -106,6 +113,7 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks(const double *__restric
             const double2 *vp = reinterpret_cast<const double2 *>(vb + vo);
             const double2 v01 = vp[0], v23 = vp[1];
             const int4 cc = load_cols4<COLT>(reinterpret_cast<const COLT *>(cb + co));
+            phi_late_args(m_stride, pstride, partial);      // (one scalar wait: it takes the slot word with it, see below)
             const double m0 = mc[cc.x], m1 = mc[cc.y], m2 = mc[cc.z], m3 = mc[cc.w];
             s = fma(v01.x, m0, s);
             s = fma(v01.y, m1, s);
@@ -116,8 +124,13 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks(const double *__restric
         } while (++it < iters);
         s = wave_sum_dpp(s);
         amax = wave_max_dpp(amax);
-        const uint32_t slot = pslot ? (uint32_t)lane_value_here(slot_ld) : chunk;      // the slot load's only wait
+        // (the slot word is a scalar load like the late arguments, so the wait for those, in the loop behind the issue of the
+        //  first stream loads, has brought it in too: no wait of its own is left here)
+        const uint32_t slot = pslot ? (uint32_t)uniform_value_here(slot_ld) : chunk;
+        char *pc = reinterpret_cast<char *>(uniform_value_here(partial)) + pdone;
         if (lane == 0) *reinterpret_cast<double2 *>(pc + slot * 16u) = make_double2(s, amax);
+        mc += uniform_value_here(m_stride);      // (not hoisted in front of the loop, where they would be waited for)
+        pdone += uniform_value_here(pstride) * (int64_t)sizeof(double2);
     }
 }
 
@@ -129,43 +142,40 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks(const double *__restric
 // output beyond n_out (the tail block streams the last real output again in its place) stores nothing.
 template <int OB, int WPB, typename COLT>
 __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__restrict__ vals, const COLT *__restrict__ cols,
-                                                           int iters, int64_t ncpo, int n_out, const double *__restrict__ m,
-                                                           int64_t m_stride, int n_cand, int64_t pstride, const int32_t *__restrict__ pslot,
-                                                           int slots_per_output, double2 *__restrict__ partial, const int32_t *__restrict__ gate)
+                                                           const double *__restrict__ m, const int32_t *__restrict__ pslot,
+                                                           int iters, uint32_t ncpo, int n_out, int n_cand, uint32_t flags,
+                                                           const int32_t *__restrict__ gate, int64_t m_stride, int64_t pstride,
+                                                           int slots_per_output, double2 *__restrict__ partial)
 {
-    kernarg_now(vals, cols, iters, ncpo, n_out, m, m_stride, n_cand, pstride, pslot, slots_per_output, partial, gate);
-    const bool closed = phi_gate_closed(gate);      // device-side predication (SPG line-search slots)
     const uint32_t chunk = phi_wave_chunk<WPB>();
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t o0 = blockIdx.y * OB;
-    if (closed) return;
-    if (chunk >= (uint32_t)ncpo) return;
+    if (flags & PHI_HAS_GATE) { if (uniform_word(gate) == 0) return; }      // device-side predication (SPG line-search slots)
+    if (chunk >= ncpo) return;
     // where the fold expects this chunk's partials: output-major chunk numbering, or the regular rows' slots (one structure for
     // all outputs).  In flight until the stores; both early exits are scalar branches without a wait of their own, so the load
     // loses nothing behind them.
-    const int32_t slot_ld = *(pslot ? pslot + chunk : reinterpret_cast<const int32_t *>(cols));
-    const uint32_t ostride = pslot ? (uint32_t)slots_per_output : (uint32_t)ncpo;
+    const int32_t slot_ld = uniform_word(pslot ? pslot + chunk : reinterpret_cast<const int32_t *>(cols));
     const uint32_t CH = (uint32_t)iters * 256u;
     const char *cb = reinterpret_cast<const char *>(cols + (uint64_t)chunk * CH);
     // output o0 + oo, clamped to the last one: each base is the one before it plus one output's entries, or the same again
-    const uint64_t per_out = (uint64_t)(uint32_t)ncpo * CH;
+    const uint64_t per_out = (uint64_t)ncpo * CH;
     const char *vb[OB];
-    vb[0] = reinterpret_cast<const char *>(vals + (uint64_t)(o0 * (uint32_t)ncpo + chunk) * CH);
+    vb[0] = reinterpret_cast<const char *>(vals + (uint64_t)(o0 * ncpo + chunk) * CH);
 #pragma unroll
     for (int oo = 1; oo < OB; oo++) vb[oo] = vb[oo - 1] + (o0 + oo < (uint32_t)n_out ? per_out * sizeof(double) : 0);
     // this lane's results after wave_sum_multi: which output, and whether this lane stores it
     constexpr int NR = wave_sum_multi_regs(OB);
-    uint32_t po[NR];
+    uint32_t on[NR];
     bool mine[NR];
 #pragma unroll
     for (int j = 0; j < NR; j++) {
-        const uint32_t o = o0 + wave_sum_multi_index<OB>(lane, j);
-        mine[j] = wave_sum_multi_owner<OB>(lane) && o < (uint32_t)n_out;
-        po[j] = o * ostride * 16u;
+        on[j] = o0 + wave_sum_multi_index<OB>(lane, j);
+        mine[j] = wave_sum_multi_owner<OB>(lane) && on[j] < (uint32_t)n_out;
     }
     const double *mc = m;
-    char *pc = reinterpret_cast<char *>(partial);
-    for (int c = 0; c < n_cand; c++, mc += m_stride, pc += pstride * (int64_t)sizeof(double2)) {
+    int64_t pdone = 0;      // candidates' partials in front of this one, in bytes
+    for (int c = 0; c < n_cand; c++) {
         double s[OB];
 #pragma unroll
         for (int oo = 0; oo < OB; oo++) s[oo] = 0.0;
@@ -180,6 +190,9 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__
                 const double2 *vp = reinterpret_cast<const double2 *>(vb[oo] + vo);
                 v01[oo] = vp[0];
                 v23[oo] = vp[1];
+                // (behind the loads of at most four outputs: the statement orders the loads around it, and OB = 8 with all sixteen
+                //  in front of it takes 100 registers instead of 62)
+                if (oo == (OB < 4 ? OB : 4) - 1) phi_late_args(m_stride, pstride, slots_per_output, partial);
             }
             const double m0 = mc[cc.x], m1 = mc[cc.y], m2 = mc[cc.z], m3 = mc[cc.w];
             amax = fmax(fmax(amax, fmax(fabs(m0), fabs(m1))), fmax(fabs(m2), fabs(m3)));
@@ -192,13 +205,19 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__
             }
             vo += 2048u; co += (uint32_t)(256 * sizeof(COLT));
         } while (++it < iters);
-        amax = wave_max_dpp(amax);
         double t[NR];
         wave_sum_multi<OB>(s, t);
-        const uint32_t slot = pslot ? (uint32_t)lane_value_here(slot_ld) : chunk;      // the slot load's only wait
+        amax = wave_max_dpp(amax);
+        // (the slot word is a scalar load like the late arguments, so the wait for those, in the loop behind the issue of the
+        //  first stream loads, has brought it in too: no wait of its own is left here)
+        const uint32_t slot = pslot ? (uint32_t)uniform_value_here(slot_ld) : chunk;
+        const uint32_t ostride = pslot ? (uint32_t)uniform_value_here(slots_per_output) : ncpo;
+        char *pc = reinterpret_cast<char *>(uniform_value_here(partial)) + pdone;
 #pragma unroll
         for (int j = 0; j < NR; j++)
-            if (mine[j]) *reinterpret_cast<double2 *>(pc + (po[j] + slot * 16u)) = make_double2(t[j], amax);
+            if (mine[j]) *reinterpret_cast<double2 *>(pc + (on[j] * ostride + slot) * 16u) = make_double2(t[j], amax);
+        mc += uniform_value_here(m_stride);      // (not hoisted in front of the loop, where they would be waited for)
+        pdone += uniform_value_here(pstride) * (int64_t)sizeof(double2);
     }
 }
 
@@ -462,14 +481,22 @@ using SolveGradKuSet = InstSet<5, 6, 8, 12>;     // KU of k_solve_grad
 using GradTilesKuSet = InstSet<5, 8, 12>;        // KU of k_grad_tiles
 using PhiObSet = InstSet<2, 4, 8>;               // OB of k_phi_chunks_shared (phi_ob)
 template <class F> static void solve_grad_ku_dispatch(int kmax, F &&launch) { SolveGradKuSet::dispatch(kmax, launch); }
+// Arguments: the first 14 dwords arrive in scalar registers with the wavefront (kernarg preload, see the chunk kernels), and they
+// hold what the fold needs in front of its first load: partial, the members of the FoldReg, rows and tiles (the descriptor fold's
+// and the ragged grid's first loads), N and nsym in one word (n_nsym = N | nsym << 8; bluest_plan_finalize checks N <= 64 and
+// nsym <= 2080), bpo and a flags word.  rec, gate and spg_state are null in the plain step: the flags say which one is there, and
+// a pointer is loaded inside the branch that uses it.  What the solving wavefront and the tile stream need behind the barrier is
+// requested in front of the fold and waited for behind the issue of its first loads (the hook given to fold_rows).
+constexpr uint32_t SG_HAS_REC = 1u, SG_HAS_GATE = 2u, SG_HAS_SPG = 4u;
 template <int NT, int KU>
-__global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int N, int n_out, const RowDesc *__restrict__ rows, int nsym, FoldReg reg,
-                                                    const double2 *__restrict__ partial, const double *__restrict__ rec, double delta,
-                                                    const TileDesc *__restrict__ tiles, int64_t n_tiles, int bpo, int tpb, int tile_nt,
+__global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(const double2 *__restrict__ partial, const uint16_t *__restrict__ rank_ab,
+                                                    const RowDesc *__restrict__ rows, const TileDesc *__restrict__ tiles,
+                                                    uint32_t n_nsym, int Cd, int Co, int bpo, uint32_t flags,
+                                                    int n_out_arg, int tpb_arg, int tile_nt, const double *__restrict__ rec_arg, double delta,
                                                     const double *__restrict__ tvals,
                                                     double *__restrict__ var, double *__restrict__ v_ws,
                                                     int32_t *__restrict__ status, double *__restrict__ grad,
-                                                    const int32_t *__restrict__ gate, double *__restrict__ spg_state, int last_slot,
+                                                    const int32_t *__restrict__ gate, double *__restrict__ spg_state_arg, int last_slot,
                                                     int32_t *__restrict__ spg_enable, unsigned int *__restrict__ ticket, const MaTail ma)
 {
     constexpr int FUSED_TPB = fused_tpb(NT, KU);
@@ -477,43 +504,48 @@ __global__ __launch_bounds__(64 * (fused_tpb(NT, KU) + 1)) void k_solve_grad(int
     constexpr int PU = tile_pairs(KU);
     __shared__ SolveLds<NT> lds;
     __shared__ double spg_ls[SPG_STATE_DOUBLES];
-    // everything in front of the fold's first load arrives in one batch (kernarg_now, common.hpp), and with it what the solving
-    // wavefront would otherwise fetch behind the barrier, one scalar round trip each on the path everybody waits for: delta and
-    // the three outputs it writes; the tile stream's arguments may follow while the fold is in flight
-    kernarg_now(N, n_out, rows, nsym, reg.Cd, reg.Co, reg.rank_ab, partial, rec, tiles, bpo, tpb, gate, spg_state, delta, var, v_ws, status);
+    const int N = (int)(n_nsym & 0xffu), nsym = (int)(n_nsym >> 8);
+    const FoldReg reg{Cd, Co, rank_ab};
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (the compiler does not see that tid >> 6 is wave-uniform)
     // which output, and am I its first workgroup: the grid says so when every output has the same number of workgroups (bpo > 0,
     // the usual case: grid = (bpo, n_out), no division), else the first tile's descriptor (grid = (workgroups, 1); one more
-    // dependent load in front of the fold)
+    // dependent load in front of the fold, and tpb is waited for in front of it)
     int o, first, wg;
     if (bpo > 0) { o = blockIdx.y; first = blockIdx.x == 0; wg = o * bpo + blockIdx.x; }
-    else { wg = blockIdx.x; const TileDesc td0 = tile_desc_uniform(tiles, (int64_t)wg * tpb); o = td0.out; first = (td0.n_valid >> 30) & 1; }
-    const int64_t t0 = (int64_t)wg * tpb;      // tpb <= FUSED_TPB tiles per workgroup (wavefronts beyond it only fold)
+    else { wg = blockIdx.x; const TileDesc td0 = tile_desc_uniform(tiles, (int64_t)wg * tpb_arg); o = td0.out; first = (td0.n_valid >> 30) & 1; }
     __shared__ int s_closed;
-    if (gate_closed(gate, &s_closed)) {
-        // predicated off; the line-search decision still has to close the slot (see k_solve_from_chunks): the first workgroups
-        // of the n_out outputs -- the ones that publish V and status and take the decision ticket when the gate is open -- arrive
-        // at a ticket of their own, and the last one decides, so none of THEM can see the gate the decision reopens.  A whole
-        // workgroup that is not the first of its output may start after that store and run: it folds the Phi partials of the
-        // accepted trial (the predicated-off Phi pass of this slot left them alone), so it rewrites that trial's gradient
-        // entries with the same bits.  The other way round (a rejected last slot closes the gate under an open launch) a late
-        // workgroup skips gradient entries of a trial nobody uses.
-        if (spg_state && first && wave == 0 && spg_closed_last(ticket + 16, (unsigned int)n_out, lane))
-            spg_decide_wave(spg_state, var, status, n_out, last_slot, spg_enable, spg_ls, lane);
-        return;
+    double *spg_state = nullptr;
+    if (flags & (SG_HAS_GATE | SG_HAS_SPG)) {      // (the line search's launches; the plain step passes this over)
+        if (flags & SG_HAS_SPG) spg_state = spg_state_arg;
+        if ((flags & SG_HAS_GATE) && gate_closed(gate, &s_closed)) {
+            // predicated off; the line-search decision still has to close the slot (see k_solve_from_chunks): the first workgroups
+            // of the n_out outputs -- the ones that publish V and status and take the decision ticket when the gate is open -- arrive
+            // at a ticket of their own, and the last one decides, so none of THEM can see the gate the decision reopens.  A whole
+            // workgroup that is not the first of its output may start after that store and run: it folds the Phi partials of the
+            // accepted trial (the predicated-off Phi pass of this slot left them alone), so it rewrites that trial's gradient
+            // entries with the same bits.  The other way round (a rejected last slot closes the gate under an open launch) a late
+            // workgroup skips gradient entries of a trial nobody uses.
+            if (spg_state && first && wave == 0 && spg_closed_last(ticket + 16, (unsigned int)n_out_arg, lane))
+                spg_decide_wave(spg_state, var, status, n_out_arg, last_slot, spg_enable, spg_ls, lane);
+            return;
+        }
     }
     SpgPrefetch pf;
     if (spg_state && first && wave == 0) spg_prefetch_state(spg_state, lane, pf);   // in flight during the fold (spg_state.hpp)
     if (N < NT) { clear_pads(lds, N, tid, NTHREADS); __syncthreads(); }   // uniform; every real entry is written by the fold
     // Phi either folded from this GPU's chunk partials, or (group-sharded plans) taken from the all-reduced record of output o:
     // N*N sums, then the per-model flags "touched with |m| > 1e-6" / "touched at all" and the flag "max|m| >= 0.05" as counts
-    const double *rec_o = rec ? rec + (int64_t)o * (N * N + 2 * N + 1) : nullptr;
+    const double *rec_o = (flags & SG_HAS_REC) ? rec_arg + (int64_t)o * (N * N + 2 * N + 1) : nullptr;
     if (rec_o) {
         for (int t = tid; t < N * N; t += NTHREADS) lds.at(t / N, t % N) = rec_o[t];
     } else {
-        fold_rows<NT>(lds, N, rows, o, nsym, partial, tid, NTHREADS, reg);
+        fold_rows<NT>(lds, N, rows, o, nsym, partial, tid, NTHREADS, reg,
+                      [&]() { kernarg_now(n_out_arg, tpb_arg, delta, var, v_ws, status); });
     }
+    // (what is computed from the late arguments stays behind the fold's loads)
+    const int n_out = uniform_value_here(n_out_arg), tpb = uniform_value_here(tpb_arg);
+    const int64_t t0 = (int64_t)wg * tpb;      // tpb <= FUSED_TPB tiles per workgroup (wavefronts beyond it only fold)
     // the list is padded to a multiple of FUSED_TPB tiles per output, so every tile of this workgroup belongs to output o
     // (loaded by the tile wavefronts only: the solving wavefront must not wait for a descriptor it does not use; scalar loads, so
     //  k, the offsets and the group count are scalar: the dispatch on k branches, the tile's and the gradient's bases are formed
@@ -1376,6 +1408,7 @@ extern "C" int bluest_plan_finalize(bluest_plan_t plan, int max_candidates)
     PhaseTimer timer("plan_finalize");
 
     plan->nsym = N * (N + 1) / 2;
+    if (N > 64 || plan->nsym > 2080) return fail(BLUEST_ERR_ARG, "N=%d: the fused kernel's argument word holds N <= 64, nsym <= 2080", N);
     plan->max_cand = max_candidates;
     plan->shared = true;
     for (int o = 1; o < n_out; o++) {
@@ -1574,11 +1607,13 @@ static void launch_solve_grad(bluest_plan_t plan, const double *rec, double delt
     const int n_out = (int)plan->outs.size();
     // (bpo, n_out) when every output has bpo workgroups -- the kernel reads its output off the grid --, else one row of workgroups
     const dim3 grid = plan->fused_bpo > 0 ? dim3((unsigned)plan->fused_bpo, (unsigned)n_out) : dim3((unsigned)(plan->n_tiles / plan->fused_tpb));
+    const uint32_t flags = (rec ? SG_HAS_REC : 0u) | (plan->gate ? SG_HAS_GATE : 0u) | (dec_state ? SG_HAS_SPG : 0u);
     nt_dispatch(plan->N, [&](auto nt) { solve_grad_ku_dispatch(plan->kmax, [&](auto ku) {
         constexpr int NT = decltype(nt)::value, KU = decltype(ku)::value;
-        hipLaunchKernelGGL((k_solve_grad<NT, KU>), grid, dim3(64 * (fused_tpb(NT, KU) + 1)), 0, st, plan->N, n_out, plan->d_rows, plan->nsym,
-                           plan->fold_reg, plan->d_partial, rec, delta, plan->d_tiles, plan->n_tiles, plan->fused_bpo, plan->fused_tpb, plan->tile_nt,
-                           plan->d_tvals, var_dev, plan->d_v, status_dev, grad_dev, plan->gate, dec_state, dec_last, dec_enable, plan->d_ticket, ma);
+        hipLaunchKernelGGL((k_solve_grad<NT, KU>), grid, dim3(64 * (fused_tpb(NT, KU) + 1)), 0, st, plan->d_partial, plan->fold_reg.rank_ab, plan->d_rows,
+                           plan->d_tiles, (uint32_t)plan->N | (uint32_t)plan->nsym << 8, plan->fold_reg.Cd, plan->fold_reg.Co, plan->fused_bpo, flags,
+                           n_out, plan->fused_tpb, (int)plan->tile_nt, rec, delta, plan->d_tvals, var_dev, plan->d_v, status_dev, grad_dev,
+                           plan->gate, dec_state, dec_last, dec_enable, plan->d_ticket, ma);
     }); });
 }
 
@@ -1612,6 +1647,7 @@ static int phi_ob(const bluest_plan_s *p, int n_cand)
 static void launch_chunks(bluest_plan_t p, const double *m, int n_cand, int64_t m_stride, hipStream_t st)
 {
     const int n_out = (int)p->outs.size();
+    const uint32_t flags = p->gate ? PHI_HAS_GATE : 0u;
     // one wavefront per workgroup of the chunk kernels (WPB = 1): single-wavefront workgroups drain earliest at the kernel's end
     // (same-box A/B at the headline size, two runs each: step 12.86 / 12.26 / 12.05 us with 4 / 2 / 1 wavefronts, 13.8 with 16)
     if (const int ob = phi_ob(p, n_cand)) {
@@ -1619,14 +1655,16 @@ static void launch_chunks(bluest_plan_t p, const double *m, int n_cand, int64_t 
         PhiObSet::dispatch(ob, [&](auto obc) {
             constexpr int OB = decltype(obc)::value;
 #define LCS2(COLT) hipLaunchKernelGGL((k_phi_chunks_shared<OB, 1, COLT>), dim3((unsigned)ncpo, (n_out + OB - 1) / OB), dim3(64), 0, st, \
-                                   p->d_vals, reinterpret_cast<const COLT *>(p->d_cols), p->iters, ncpo, n_out, m, m_stride, n_cand, p->partial_stride, p->d_pslot, p->slots_per_output, p->d_partial, p->gate)
+                                   p->d_vals, reinterpret_cast<const COLT *>(p->d_cols), m, p->d_pslot, p->iters, (uint32_t)ncpo, n_out, n_cand, flags, \
+                                   p->gate, m_stride, p->partial_stride, p->slots_per_output, p->d_partial)
             if (p->cols16) LCS2(uint16_t); else LCS2(int32_t);
 #undef LCS2
         });
         return;
     }
 #define LPC(COLT) hipLaunchKernelGGL((k_phi_chunks<1, COLT>), dim3((unsigned)p->n_chunks), dim3(64), 0, st, p->d_vals, \
-                                  reinterpret_cast<const COLT *>(p->d_cols), p->iters, p->n_chunks, m, m_stride, n_cand, p->d_partial, p->d_pslot, p->partial_stride, p->gate)
+                                  reinterpret_cast<const COLT *>(p->d_cols), m, p->d_pslot, p->iters, (uint32_t)p->n_chunks, n_out, n_cand, flags, \
+                                  p->gate, m_stride, p->partial_stride, p->slots_per_output, p->d_partial)
     if (p->cols16) LPC(uint16_t); else LPC(int32_t);
 #undef LPC
 }

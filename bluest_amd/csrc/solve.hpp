@@ -98,9 +98,13 @@ __device__ __forceinline__ double opaque_zero()
 // row does not use stay zero -- so the fold needs no descriptor: one memory round trip instead of two dependent ones
 // (descriptor -> partials), measured 0.47 us of the 1.5 us fold at the headline size.  Cd = 0: the descriptor path.
 struct FoldReg { int Cd, Co; const uint16_t *rank_ab; };     // rank_ab[r] = a | b << 8 of the destination with rank r
-template <int NT>
+// issued(): the caller's hook behind the ISSUE of a row's partial loads and in front of their first use -- the place for the wait
+// on kernel arguments the fold does not need (kernarg_now there: their round trip runs under the partials').
+struct FoldNoHook { __device__ __forceinline__ void operator()() const {} };
+template <int NT, class Hook = FoldNoHook>
 __device__ __forceinline__ void fold_rows(SolveLds<NT> &lds, int N, const RowDesc *__restrict__ rows, int o,
-                                          int n_rows, const double2 *__restrict__ partial, int tid, int nthreads, FoldReg reg)
+                                          int n_rows, const double2 *__restrict__ partial, int tid, int nthreads, FoldReg reg,
+                                          const Hook &issued = Hook())
 {   // the output's rows are rows[o * n_rows ..) and, regular, its partials partial[o * slots ..): no division by n_rows
     const int q = tid & 3;
     if (reg.Cd > 0) {
@@ -116,6 +120,7 @@ __device__ __forceinline__ void fold_rows(SolveLds<NT> &lds, int N, const RowDes
                 double2 v[8];
 #pragma unroll
                 for (int i = 0; i < 8; i++) v[i] = (c0 + 4 * i < n) ? p[c0 + 4 * i] : make_double2(0.0, 0.0);
+                issued();
 #pragma unroll
                 for (int i = 0; i < 8; i++) { s += v[i].x; am = fmax(am, v[i].y); }
             }
@@ -141,6 +146,7 @@ __device__ __forceinline__ void fold_rows(SolveLds<NT> &lds, int N, const RowDes
             double2 v[8];
 #pragma unroll
             for (int i = 0; i < 8; i++) v[i] = (c0 + 4 * i < n) ? p[c0 + 4 * i] : make_double2(0.0, 0.0);
+            issued();
 #pragma unroll
             for (int i = 0; i < 8; i++) { s += v[i].x; am = fmax(am, v[i].y); }
         }

@@ -2,20 +2,25 @@
 """
 Static instruction counts of the evaluation step's kernels from a device listing of csrc/plan.hip:
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S -Iinclude -Ibluest_amd/csrc bluest_amd/csrc/plan.hip -o plan.s
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S -Iinclude -Ibluest_amd/csrc \
+          -mllvm -amdgpu-kernarg-preload-count=16 bluest_amd/csrc/plan.hip -o plan.s      (the unit's flags of bluest_amd/build.py)
     python tools/isa_counts.py plan.s
 
 Per Phi kernel: all instructions of the listing (every block once -- which is what a wavefront executes when iters = 1 and
 n_cand = 1, minus the block a branch skips), split into VALU / SALU / VMEM / SMEM, the instructions in front of the first
-streaming load, those behind the loop's last FMA (the tail), the waits in front of the stream, and the registers.
+streaming load, those behind the loop's last FMA (the tail), the waits in front of the stream, the registers and the number of
+argument dwords the descriptor has preloaded into scalar registers (kernarg preload); then the loads, barriers and waits from the
+entry to the first streaming load.  A kernel with preloaded arguments is read from its preload entry (preload_entry).
 For k_solve_grad<20,5>: the instruction counts of four regions (solve_regions: entry -> first fold load along the shortest path,
 the fold, the tile stream and the solving wavefront between the barriers, the tile wavefronts behind the second barrier) and the
-registers; then the line numbers (relative to the kernel's start) of the descriptor load, the late kernarg loads, the
+registers, with the loads, barriers and waits along the path of region (1); then the line numbers (relative to the kernel's start,
+in the order of the text) of the descriptor load, the late kernarg loads, the
 first load of the fold, the barriers and the first non-temporal tile load, with the waits between the first barrier and that load.
 """
 import re
 import sys
 
+# (prefixes of the mangled names: the argument lists may change)
 PHI = [("k_phi_chunks_shared<%d,1,uint16_t>" % ob, "_Z19k_phi_chunks_sharedILi%dELi1EtE" % ob) for ob in (2, 4, 8)]
 PHI.append(("k_phi_chunks<1,uint16_t>", "_Z12k_phi_chunksILi1EtE"))
 SOLVE = ("k_solve_grad<20,5>", "_Z12k_solve_gradILi20ELi5EE")
@@ -30,7 +35,27 @@ def kernel_body(lines, prefix):
         if m:
             meta[m.group(1)] = int(m.group(2))
     meta.setdefault("NumSgprs", meta.get("TotalNumSgprs", -1))
-    return start, [l for l in lines[start + 1:end + 1]], meta
+    meta["Preload"] = 0
+    for l in lines[start:end]:      # the kernel descriptor stands between s_endpgm and .Lfunc_end
+        m = re.match(r"\s*\.amdhsa_user_sgpr_kernarg_preload_length\s+(\d+)", l)
+        if m:
+            meta["Preload"] = int(m.group(1))
+    body = [l for l in lines[start + 1:end + 1]]
+    return start, body[preload_entry(body):], meta
+
+
+def preload_entry(body):
+    """A kernel with preloaded arguments (kernarg preload, descriptor field preload_length > 0) begins with a prologue for firmware
+    without the feature: it loads those arguments from the argument segment, waits and branches to the entry proper, the block
+    behind the next `.p2align 8`, where a wavefront whose arguments were preloaded starts.  Index of that block's first line
+    (0: no prologue); every count and every "from the kernel's entry" below starts there."""
+    for i, l in enumerate(body[:40]):
+        t = l.strip()
+        if re.match(r"\.p2align\s+8", t):
+            return i + 1
+        if t and not t.startswith((";", "s_load_dword", "s_waitcnt", "s_branch", "s_nop")):
+            break
+    return 0
 
 
 def instrs(body):
@@ -65,16 +90,28 @@ def phi_report(name, body, meta):
     first = stream[0]
     fmas = [i for i, x in enumerate(ins) if x.startswith(("v_fmac_f64", "v_fma_f64"))]
     waits = [x for x in ins[:first] if x.startswith("s_waitcnt")]
-    print("%-36s total %4d  VALU %4d  SALU %4d  VMEM %3d  SMEM %3d | before the stream %3d (waits: %s) | tail %3d | VGPRs %3d  SGPRs %3d  occupancy %d" %
+    print("%-36s total %4d  VALU %4d  SALU %4d  VMEM %3d  SMEM %3d | before the stream %3d (waits: %s) | tail %3d | VGPRs %3d  SGPRs %3d  occupancy %d  preload %d" %
           (name, len(ins), n["VALU"], n["SALU"], n["VMEM"], n["SMEM"], first, ", ".join(w.replace("s_waitcnt ", "") for w in waits) or "none",
-           len(ins) - 1 - fmas[-1], meta.get("NumVgprs", -1), meta.get("NumSgprs", -1), meta.get("Occupancy", -1)))
+           len(ins) - 1 - fmas[-1], meta.get("NumVgprs", -1), meta.get("NumSgprs", -1), meta.get("Occupancy", -1), meta["Preload"]))
+
+
+def entry_report(name, body):
+    """loads, barriers and waits of a Phi kernel from its entry to the first load of the stream"""
+    ins = instrs(body)
+    first = next(i for i, x in enumerate(ins) if re.match(r"global_load_dwordx(2|4)", x))
+    print(name)
+    for i, x in enumerate(ins[:first + 1]):
+        if x.startswith(("s_load", "s_buffer_load", "global_load", "s_barrier", "s_waitcnt")):
+            print("   %5d  %s%s" % (i, x, "      <- first load of the stream" if i == first else ""))
 
 
 def solve_report(name, body):
     ins = instrs(body)
     print(name)
     barrier = [i for i, x in enumerate(ins) if x.startswith("s_barrier")]
-    marks = []
+    ush = next(i for i, x in enumerate(ins) if x.startswith("global_load_ushort"))      # (the regular fold's rank_ab load)
+    fold = next(i for i in range(ush, len(ins)) if ins[i].startswith("global_load_dwordx4"))
+    marks = [(fold, ins[fold] + "      <- first partial load of the regular fold")]
     for i, x in enumerate(ins):
         if x.startswith("s_load"):
             marks.append((i, x))
@@ -167,14 +204,18 @@ def solve_regions(name, body, meta):
             if nd < dist.get(nb, 1 << 30):
                 dist[nb] = nd
                 heapq.heappush(heap, (nd, nb, path + [nb]))
-    print(name + "   VGPRs %d  SGPRs %d  scratch %d  occupancy %d" % (meta.get("NumVgprs", -1), meta.get("NumSgprs", -1),
-                                                                     meta.get("ScratchSize", -1), meta.get("Occupancy", -1)))
+    print(name + "   VGPRs %d  SGPRs %d  scratch %d  occupancy %d  preload %d" % (meta.get("NumVgprs", -1), meta.get("NumSgprs", -1),
+                                                                                 meta.get("ScratchSize", -1), meta.get("Occupancy", -1), meta["Preload"]))
     if best is None:
         print("   (1) entry -> first fold load: no path without a vector load, an LDS operation or a barrier")
     else:
         head = [x for b in best[1][:-1] for x in bl[b][1]] + bl[tb][1][:tj]
         print("   (1) entry -> first fold load        %s   waits on the way: %s" % (
             tally(head), ", ".join(x.replace("s_waitcnt ", "") for x in head if x.startswith("s_waitcnt")) or "none"))
+        print("       loads, barriers and waits on that path (numbered along the path):")
+        for i, x in enumerate(head):
+            if x.startswith(("s_load", "s_buffer_load", "global_load", "s_barrier", "s_waitcnt")):
+                print("          %4d  %s" % (i, x))
     bar = [i for i, x in enumerate(text) if x.startswith("s_barrier")]
     b1 = next(i for i in bar if i > first)
     b2 = next(i for i in bar if i > b1)
@@ -191,6 +232,8 @@ def main():
     for name, prefix in PHI:
         _, body, meta = kernel_body(lines, prefix)
         phi_report(name, body, meta)
+    for name, prefix in PHI:
+        entry_report(name, kernel_body(lines, prefix)[1])
     _, body, meta = kernel_body(lines, SOLVE[1])
     solve_regions(SOLVE[0], body, meta)
     solve_report(SOLVE[0], body)
