@@ -2,6 +2,7 @@
 ctypes binding of libbluest_hip.so (include/bluest_hip.h).  There is no CPU fallback: if the library is
 missing, or no GPU is visible, every compute call raises BluestHipError.
 """
+import contextlib
 import ctypes
 import os
 
@@ -156,6 +157,18 @@ def ptr(a):
     if hasattr(a, "data_ptr"):
         return a.data_ptr()
     return a.ctypes.data
+
+
+@contextlib.contextmanager
+def staging_budget(slab_bytes):
+    """with staging_budget(slab_bytes): ... -- the sample-sum calls inside stage host segments in slabs of at most `slab_bytes`
+    (bluest_group_sums_slab).  The budget is process-wide: it is left as it was."""
+    before = c_i64(0)
+    check(lib().bluest_group_sums_slab(max(int(slab_bytes), 1), ctypes.byref(before)))
+    try:
+        yield
+    finally:
+        lib().bluest_group_sums_slab(before.value, None)
 
 
 class capture_guard(object):

@@ -2,9 +2,9 @@
 // z_i[c] = sum_j coef_j (y_ij[c] - y_0j[c]), the BLUE-weighted combination of a group's models: what the sampled variance of every
 // component of a field estimate is made of.
 //
-// The segments, the chunk table, the slabs of staged host data and the fold over the chunks are those of gsums.hip, fields.hip and
-// moments.hip; the first-sample rows of the host segments travel in a buffer of their own, as in moments.hip, so a chunk in a later
-// slab still finds its segment's shift.  What is new is the work of a chunk.  A row of a segment is W = L d contiguous doubles,
+// The segments, the chunk table and the slabs of staged host data are those of staging.hpp, the fold over the chunks is that of
+// fields.hip; the first-sample rows of the host segments travel in a buffer of their own, as in moments.hip, so a chunk in a later
+// slab still finds its segment's shift.  What is its own is the work of a chunk.  A row of a segment is W = L d contiguous doubles,
 // [model j][component c], and the chain of z over j walks it with stride d.  Per call one k_fmom_* launch per slab (device
 // segments: one launch for all of them; two where only some segments take the split form of k_fmom_wide) and one k_fmom_fold,
 // no atomics, nothing sized by the device.  The shape follows d and W (field_moments_rows and field_moments_split, decided on
@@ -40,15 +40,12 @@
 namespace {
 
 constexpr int BLK = 256;                            // k_fmom_staged, k_fmom_fold
-constexpr int CHUNK = BLUEST_GSUM_CHUNK;
-constexpr int CLASSES = 8, CLASS_ROWS = CHUNK / CLASSES;
 constexpr int WIDE_COLS = WAVE;                     // components per workgroup of k_fmom_wide, and the least d it takes
 constexpr int WIDE_BLK = CLASSES * WIDE_COLS;
 constexpr int STAGE_DOUBLES = 4096;                 // LDS of a k_fmom_staged workgroup where one row fits it
 constexpr int FOLD_COLS = 64;
 constexpr int SPLIT_FROM_L = 16, SPLIT_BELOW_D = 16 * WIDE_COLS;
 constexpr int LOADS = 4;                            // 16-byte loads a thread keeps in flight while it stages
-static_assert(CLASSES * CLASS_ROWS == CHUNK && CLASS_ROWS == 16, "the row classes tile the chunk");
 static_assert((size_t)BLUEST_MAX_MODELS * WIDE_COLS * 8 + 2 * WIDE_BLK * 8 <= 64 * 1024, "shift and class sums of k_fmom_wide fit the default LDS");
 static_assert(CLASSES * (WIDE_COLS - 1) <= 2 * BLK, "two passes of k_fmom_staged cover every (class, component)");
 
@@ -64,7 +61,7 @@ bool field_moments_split(int L, int64_t d) { return d >= WIDE_COLS && d < SPLIT_
 int field_moments_rows(int L, int64_t d)
 {
     if (d >= WIDE_COLS) return 0;
-    int sb = CHUNK;
+    int sb = GCHUNK;
     while (sb > 1 && staged_doubles(L * (int)d, (int)d, sb) > STAGE_DOUBLES) sb >>= 1;
     return sb;
 }
@@ -83,11 +80,6 @@ struct ZSeg {
     int64_t nchunks;
     int64_t split;          // 1: a chunk's partial sums are its eight class sums [class][2 d], still to be joined
 };
-
-__device__ __forceinline__ double class_tree(const double *c, int stride)
-{
-    return ((c[0] + c[stride]) + (c[2 * stride] + c[3 * stride])) + ((c[4 * stride] + c[5 * stride]) + (c[6 * stride] + c[7 * stride]));
-}
 
 // z of the rows r, r + 1, r + 2, r + 3 of one component, their chains side by side: the loads of four rows are in flight together
 __device__ __forceinline__ void chains4(const double *p, int64_t W, int64_t d, int L, const double *sh, const double *__restrict__ cf,
@@ -313,12 +305,6 @@ __global__ __launch_bounds__(BLK) void k_fmom_fold(const ZSeg *__restrict__ segs
     }
 }
 
-struct Piece {              // rows [first, first + rows) of a host segment, staged at `at` bytes of its slab
-    int64_t seg, first, rows;
-    size_t at;
-    int slab;
-};
-
 }  // namespace
 
 extern "C" int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t *counts, const int32_t *sizes,
@@ -328,20 +314,14 @@ extern "C" int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t
     if (d < 1) return fail(BLUEST_ERR_ARG, "d=%lld: at least one component is needed", (long long)d);
     if (!counts || !sizes || !values || !coef || !zsum || !zsq) return fail(BLUEST_ERR_ARG, "null pointer");
     int64_t T = 0, nchunks = 0;
-    int Lmax = 1;
     for (int64_t s = 0; s < S; s++) {
-        if (sizes[s] < 1 || sizes[s] > BLUEST_MAX_MODELS)
-            return fail(BLUEST_ERR_ARG, "sizes[%lld]=%d out of range (1..%d)", (long long)s, sizes[s], BLUEST_MAX_MODELS);
-        if (counts[s] < 0) return fail(BLUEST_ERR_ARG, "counts[%lld]=%lld is negative", (long long)s, (long long)counts[s]);
-        if (counts[s] > 0 && !values[s]) return fail(BLUEST_ERR_ARG, "values[%lld] is null", (long long)s);
-        if (counts[s] > 0 && ((uintptr_t)values[s] & 7)) return fail(BLUEST_ERR_ARG, "values[%lld] is not 8-byte aligned", (long long)s);
+        int rc = check_segment(s, counts, sizes, values); if (rc) return rc;
         T += sizes[s];
-        nchunks += (counts[s] + CHUNK - 1) / CHUNK;
-        Lmax = std::max(Lmax, (int)sizes[s]);
+        nchunks += (counts[s] + GCHUNK - 1) / GCHUNK;
     }
     const int64_t ncb = (d + WIDE_COLS - 1) / WIDE_COLS;
     if (T > 0x7fffffffLL || nchunks > 0x7fffffffLL || (double)T * (double)d > 2147483647.0 || (double)S * (double)d > 2147483647.0)
-        return fail(BLUEST_ERR_ARG, "more than 2^31 - 1 columns, column-components (T d), values (S d) or chunks of %d samples in one call", CHUNK);
+        return fail(BLUEST_ERR_ARG, "more than 2^31 - 1 columns, column-components (T d), values (S d) or chunks of %d samples in one call", GCHUNK);
     if ((double)nchunks * (double)ncb * CLASSES > 2147483647.0)
         return fail(BLUEST_ERR_ARG, "more than 2^31 - 1 (chunk, block of %d components, class) workgroups in one call", WIDE_COLS);
     for (int64_t t = 0; t < T; t++)
@@ -350,22 +330,25 @@ extern "C" int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t
     hipStream_t st = (hipStream_t)stream;
     const bool wide = d >= WIDE_COLS;
 
-    // ---- the tables: segments, chunks per slab (device segments are "slab" 0, read in place) ----
+    // ---- the tables: segments ----
     std::vector<ZSeg> segs((size_t)S);
     std::vector<int64_t> col0((size_t)S), shift_at((size_t)S, -1);    // host segments: where the first-sample row [L d] lies in the shift buffer
-    std::vector<char> device((size_t)S);
+    std::vector<char> device((size_t)S), staged((size_t)S);
+    std::vector<size_t> row_bytes((size_t)S);
     int64_t nshift = 0, npart = 0;
     {
         int64_t col = 0;
         for (int64_t s = 0; s < S; s++) {
-            const int64_t nc = (counts[s] + CHUNK - 1) / CHUNK;
+            const int64_t nc = (counts[s] + GCHUNK - 1) / GCHUNK;
             const int64_t per_chunk = 2 * d * (field_moments_split(sizes[s], d) ? CLASSES : 1);
             segs[s] = ZSeg{npart, nc, per_chunk != 2 * d};
             col0[s] = col;
             col += sizes[s];
             npart += nc * per_chunk;
             device[s] = counts[s] > 0 && on_device(values[s]);
-            if (counts[s] > 0 && !device[s]) {
+            staged[s] = counts[s] > 0 && !device[s];
+            row_bytes[s] = (size_t)sizes[s] * d * 8;
+            if (staged[s]) {
                 shift_at[s] = nshift;
                 nshift += sizes[s] * d;
             }
@@ -375,82 +358,40 @@ extern "C" int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t
     for (int64_t s = 0; s < S; s++)
         if (shift_at[s] >= 0) std::memcpy(shifts.data() + shift_at[s], values[s], (size_t)sizes[s] * d * 8);
 
-    // slabs of the staging buffer: whole chunks only, each piece 256-byte aligned; a slab holds at least one chunk
-    int64_t slab_bytes = 0;
-    rc = bluest_group_sums_slab(0, &slab_bytes); if (rc) return rc;
-    const size_t budget = std::max<size_t>((size_t)slab_bytes, (size_t)CHUNK * Lmax * d * 8 + 256);
-    std::vector<Piece> pieces;
-    std::vector<size_t> slab_used;              // bytes per slab
-    {
-        size_t used = 0;
-        int slab = 0;
-        bool open = false;
-        for (int64_t s = 0; s < S; s++) {
-            if (device[s] || counts[s] == 0) continue;
-            const size_t row_bytes = (size_t)sizes[s] * d * 8;
-            int64_t a = 0;
-            while (a < counts[s]) {
-                const int64_t rest = counts[s] - a;
-                int64_t fit = (int64_t)((budget - used) / row_bytes);
-                if (fit < rest) fit -= fit % CHUNK;
-                if (fit <= 0) {                 // (an empty slab always fits a chunk: budget >= the widest chunk)
-                    slab_used.push_back(used);
-                    slab++;
-                    used = 0;
-                    continue;
-                }
-                const int64_t rows = std::min(rest, fit);
-                pieces.push_back(Piece{s, a, rows, used, slab});
-                used = std::min(budget, (used + (size_t)rows * row_bytes + 255) & ~(size_t)255);
-                open = true;
-                a += rows;
-            }
-        }
-        if (open) slab_used.push_back(used);
-    }
-    const size_t stage_bytes = slab_used.empty() ? 0 : *std::max_element(slab_used.begin(), slab_used.end());
-    const size_t n_slabs = slab_used.size();
+    const SlabPlan plan = plan_slabs(S, counts, row_bytes.data(), staged.data(), GCHUNK, (size_t)slab_budget());
+    const size_t n_groups = 1 + plan.slab_used.size();
 
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    DeviceArena arena;
     const size_t b_out = (size_t)S * d * 8;
-    const size_t o_stage = take(stage_bytes + 256), o_shift = take((size_t)nshift * 8), o_part = take((size_t)npart * 8),
-                 o_chunks = take((size_t)nchunks * sizeof(ZChunk)), o_segs = take((size_t)S * sizeof(ZSeg)), o_coef = take((size_t)T * 8),
-                 o_zsum = take(b_out), o_zsq = take(b_out);
-    char *dv = nullptr;
-    HIP_TRY(hipMalloc(&dv, off));
-    struct Free { char *p; ~Free() { if (p) (void)hipFree(p); } } guard{dv};
+    const size_t o_stage = arena.take(plan.stage_bytes + 256), o_shift = arena.take((size_t)nshift * 8), o_part = arena.take((size_t)npart * 8),
+                 o_chunks = arena.take((size_t)nchunks * sizeof(ZChunk)), o_segs = arena.take((size_t)S * sizeof(ZSeg)),
+                 o_coef = arena.take((size_t)T * 8), o_zsum = arena.take(b_out), o_zsq = arena.take(b_out);
+    HIP_TRY(arena.alloc());
+    char *dv = arena.base;
     const double *d_stage = (const double *)(dv + o_stage), *d_shift = (const double *)(dv + o_shift), *d_coef = (const double *)(dv + o_coef);
     double *d_part = (double *)(dv + o_part), *d_zsum = (double *)(dv + o_zsum), *d_zsq = (double *)(dv + o_zsq);
     ZChunk *d_chunks = (ZChunk *)(dv + o_chunks);
 
-    // the chunks of launch (g, split), g = 0 for the device segments and 1 + slab for a slab, lie together in the table
-    std::vector<std::vector<ZChunk>> lists(2 * (1 + n_slabs));
-    std::vector<int> lds_doubles(2 * (1 + n_slabs), 0);
+    // ---- the chunks: launch group 0 reads the device segments where they lie, group 1 + k the pieces of slab k; the split
+    // segments of a group have a list of their own ----
+    ChunkLists<ZChunk> chunks(n_groups, 2, nchunks);
+    std::vector<int> lds_doubles(2 * n_groups, 0);
     auto add_chunks = [&](size_t g, int64_t s, const double *base, int64_t first_row, int64_t rows, const double *shift) {
         const int L = sizes[s], sb = field_moments_rows(L, d);
         const int64_t W = (int64_t)L * d, per_chunk = segs[s].split ? 2 * d * CLASSES : 2 * d;
-        g = 2 * g + (size_t)segs[s].split;
-        lds_doubles[g] = std::max(lds_doubles[g], wide ? L * WIDE_COLS + 2 * WIDE_BLK : staged_doubles((int)W, (int)d, sb));
-        for (int64_t a = 0; a < rows; a += CHUNK)
-            lists[g].push_back(ZChunk{base + a * W, shift, segs[s].part + ((first_row + a) / CHUNK) * per_chunk,
-                                      (int32_t)std::min<int64_t>(CHUNK, rows - a), L, (int32_t)col0[s], sb});
+        int &lds = lds_doubles[2 * g + (size_t)segs[s].split];
+        lds = std::max(lds, wide ? L * WIDE_COLS + 2 * WIDE_BLK : staged_doubles((int)W, (int)d, sb));
+        for (int64_t a = 0; a < rows; a += GCHUNK)
+            chunks.add(g, (size_t)segs[s].split, ZChunk{base + a * W, shift, segs[s].part + ((first_row + a) / GCHUNK) * per_chunk,
+                                                        (int32_t)std::min<int64_t>(GCHUNK, rows - a), L, (int32_t)col0[s], sb});
     };
     for (int64_t s = 0; s < S; s++)
         if (device[s]) add_chunks(0, s, values[s], 0, counts[s], values[s]);
-    for (const Piece &pc : pieces) add_chunks(1 + (size_t)pc.slab, pc.seg, d_stage + pc.at / 8, pc.first, pc.rows, d_shift + shift_at[pc.seg]);
-    std::vector<ZChunk> chunks;
-    chunks.reserve((size_t)nchunks);
-    std::vector<size_t> list0(lists.size() + 1);
-    for (size_t i = 0; i < lists.size(); i++) {
-        list0[i] = chunks.size();
-        chunks.insert(chunks.end(), lists[i].begin(), lists[i].end());
-    }
-    list0[lists.size()] = chunks.size();
-    if ((int64_t)chunks.size() != nchunks) return fail(BLUEST_ERR_HIP, "internal: %zu chunks tabled, %lld expected", chunks.size(), (long long)nchunks);
+    for (const Piece &pc : plan.pieces) add_chunks(1 + (size_t)pc.slab, pc.seg, d_stage + pc.at / 8, pc.first, pc.rows, d_shift + shift_at[pc.seg]);
+    rc = chunks.flatten(); if (rc) return rc;
     // the tables lie side by side on the device: one image of them on the host, one copy
     std::vector<char> tables(o_zsum - o_chunks);
-    if (nchunks > 0) std::memcpy(tables.data(), chunks.data(), (size_t)nchunks * sizeof(ZChunk));
+    if (nchunks > 0) std::memcpy(tables.data(), chunks.table.data(), (size_t)nchunks * sizeof(ZChunk));
     std::memcpy(tables.data() + (o_segs - o_chunks), segs.data(), (size_t)S * sizeof(ZSeg));
     std::memcpy(tables.data() + (o_coef - o_chunks), coef, (size_t)T * 8);
     HIP_TRY(hipMemcpyAsync(dv + o_chunks, tables.data(), tables.size(), hipMemcpyHostToDevice, st));
@@ -458,7 +399,7 @@ extern "C" int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t
 
     auto launch_group = [&](size_t g) -> hipError_t {
         for (size_t split = 0; split < 2; split++) {
-            const size_t c0 = list0[2 * g + split], c1 = list0[2 * g + split + 1];
+            const size_t c0 = chunks.begin(g, split), c1 = chunks.end(g, split);
             if (c1 <= c0) continue;
             const size_t lds = (size_t)lds_doubles[2 * g + split] * 8;
             const ZChunk *table = d_chunks + c0;
@@ -471,16 +412,7 @@ extern "C" int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t
         }
         return hipSuccess;
     };
-    HIP_TRY(launch_group(0));
-    for (size_t p = 0; p < pieces.size();) {
-        const int slab = pieces[p].slab;
-        for (; p < pieces.size() && pieces[p].slab == slab; p++) {
-            const Piece &pc = pieces[p];
-            const int64_t W = (int64_t)sizes[pc.seg] * d;
-            HIP_TRY(hipMemcpyAsync(dv + o_stage + pc.at, values[pc.seg] + pc.first * W, (size_t)pc.rows * W * 8, hipMemcpyHostToDevice, st));
-        }
-        HIP_TRY(launch_group(1 + (size_t)slab));                          // in stream order: the next slab's copies wait for it
-    }
+    rc = run_slabs(plan, dv + o_stage, values, counts, row_bytes.data(), 1, launch_group, st); if (rc) return rc;
     const dim3 gf((unsigned)S, (unsigned)std::min<int64_t>((2 * d + FOLD_COLS - 1) / FOLD_COLS, 65535));
     hipLaunchKernelGGL(k_fmom_fold, gf, dim3(BLK), 0, st, (const ZSeg *)(dv + o_segs), (const double *)d_part, d, d_zsum, d_zsq);
     HIP_TRY(hipGetLastError());

@@ -22,6 +22,8 @@
 //   k_fsum_fold         grid (segment, block of 64 column-components): wave g = 0..3 computes the lane sums l = g, g + 4, ... of
 //                       Part 11 step 3 for its 64 columns into LDS (coalesced along the columns), then the tree runs over LDS.
 //   k_fsum_mu           a thread per (repeat, component): the fma chain over the repeat's columns in ascending order.
+// The segments' checks, the slabs of staged host data, the chunk table and the slab loop of bluest_field_sums are those of
+// staging.hpp; bluest_field_stats has one array and cuts it into slabs of whole chunks itself.
 #include "staging.hpp"
 
 namespace {
@@ -219,10 +221,7 @@ __global__ __launch_bounds__(BLK) void k_field_fold_comp(FieldShape sh, const in
 }
 
 // ---- bluest_field_sums ---------------------------------------------------------------------------------------------------------
-constexpr int GCHUNK = BLUEST_GSUM_CHUNK;
-constexpr int CLASSES = 8, CLASS_ROWS = GCHUNK / CLASSES;
 constexpr int FOLD_COLS = 64;
-static_assert(CLASSES * CLASS_ROWS == GCHUNK, "the row classes tile the chunk");
 
 struct FChunk {
     const double *src;      // row 0 of the chunk (device address)
@@ -254,7 +253,7 @@ __global__ __launch_bounds__(BLK) void k_fsum_partial(const FChunk *__restrict__
                 for (int r = k * CLASS_ROWS; r < r1; r++) q[k] += src[(int64_t)r * ch.W];
             }
         }
-        part[ch.part + col] = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
+        part[ch.part + col] = class_tree(q);
     }
 }
 
@@ -293,19 +292,6 @@ __global__ __launch_bounds__(BLK) void k_fsum_mu(int64_t d, const int64_t *__res
     }
 }
 
-struct Piece {              // rows [first, first + rows) of a host segment, staged at `at` bytes of its slab
-    int64_t seg, first, rows;
-    size_t at;
-    int slab;
-};
-
-int64_t slab_budget()
-{
-    int64_t bytes = BLUEST_GSUM_SLAB_BYTES;
-    (void)bluest_group_sums_slab(0, &bytes);
-    return bytes;
-}
-
 }  // namespace
 
 extern "C" int bluest_field_stats(int64_t N, int L, int64_t d, const double *values, const double *w, double *sumse, double *sumsc,
@@ -339,15 +325,13 @@ extern "C" int bluest_field_stats(int64_t N, int L, int64_t d, const double *val
     const size_t chunk_bytes = (size_t)CHUNK * L * d * 8;
     const int64_t slab_chunks = staged ? std::min<int64_t>(sh.nchunks, std::max<int64_t>(1, slab_budget() / (int64_t)chunk_bytes)) : sh.nchunks;
     const size_t mat = (size_t)L * L * 8, vec = (size_t)L * d * 8, dvec = (size_t)P * d * 8;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_in = take(staged ? (size_t)std::min<int64_t>(N, slab_chunks * CHUNK) * L * d * 8 : 0), o_w = take((size_t)d * 8),
-                 o_pp = take((size_t)(diff ? 2 : 1) * npairs * sh.nchunks * sh.ntiles * 8), o_pe = take((size_t)sh.nchunks * vec),
-                 o_pd = take(diff ? (size_t)sh.nchunks * npairs * d * 8 : 0), o_q = take(diff ? (size_t)P * 4 : 0), o_se = take(vec),
-                 o_sc = take(mat), o_d1 = take(diff ? dvec : 0), o_d2 = take(diff ? mat : 0);
-    char *dv = nullptr;
-    HIP_TRY(hipMalloc(&dv, off));
-    struct Free { char *p; ~Free() { if (p) (void)hipFree(p); } } guard{dv};
+    DeviceArena arena;
+    const size_t o_in = arena.take(staged ? (size_t)std::min<int64_t>(N, slab_chunks * CHUNK) * L * d * 8 : 0), o_w = arena.take((size_t)d * 8),
+                 o_pp = arena.take((size_t)(diff ? 2 : 1) * npairs * sh.nchunks * sh.ntiles * 8), o_pe = arena.take((size_t)sh.nchunks * vec),
+                 o_pd = arena.take(diff ? (size_t)sh.nchunks * npairs * d * 8 : 0), o_q = arena.take(diff ? (size_t)P * 4 : 0),
+                 o_se = arena.take(vec), o_sc = arena.take(mat), o_d1 = arena.take(diff ? dvec : 0), o_d2 = arena.take(diff ? mat : 0);
+    HIP_TRY(arena.alloc());
+    char *dv = arena.base;
     double *d_w = (double *)(dv + o_w), *d_pp = (double *)(dv + o_pp), *d_pe = (double *)(dv + o_pe), *d_pd = (double *)(dv + o_pd);
     double *d_se = (double *)(dv + o_se), *d_sc = (double *)(dv + o_sc), *d_d1 = (double *)(dv + o_d1), *d_d2 = (double *)(dv + o_d2);
     int32_t *d_q = (int32_t *)(dv + o_q);
@@ -404,16 +388,7 @@ extern "C" int bluest_field_sums(int64_t S, int64_t d, const int64_t *counts, co
     double npart_f = 0.0;
     int Lmax = 1;
     for (int64_t s = 0; s < S; s++) {
-        if (sizes[s] < 1 || sizes[s] > BLUEST_MAX_MODELS)
-            return fail(BLUEST_ERR_ARG, "sizes[%lld]=%d out of range (1..%d)", (long long)s, sizes[s], BLUEST_MAX_MODELS);
-        if (counts[s] < 0) return fail(BLUEST_ERR_ARG, "counts[%lld]=%lld is negative", (long long)s, (long long)counts[s]);
-        if (counts[s] > 0 && !values[s]) return fail(BLUEST_ERR_ARG, "values[%lld] is null", (long long)s);
-        if (counts[s] > 0 && ((uintptr_t)values[s] & 7)) return fail(BLUEST_ERR_ARG, "values[%lld] is not 8-byte aligned", (long long)s);
-        if (weights) {
-            if (repeat_of[s] < 0 || repeat_of[s] >= R)
-                return fail(BLUEST_ERR_ARG, "repeat_of[%lld]=%lld out of range (0..%d)", (long long)s, (long long)repeat_of[s], R - 1);
-            if (s > 0 && repeat_of[s] < repeat_of[s - 1]) return fail(BLUEST_ERR_ARG, "repeat_of decreases at segment %lld", (long long)s);
-        }
+        int rc = check_segment(s, counts, sizes, values, weights ? repeat_of : nullptr, R); if (rc) return rc;
         const int64_t nc = (counts[s] + GCHUNK - 1) / GCHUNK;
         T += sizes[s];
         nchunks += nc;
@@ -425,12 +400,11 @@ extern "C" int bluest_field_sums(int64_t S, int64_t d, const int64_t *counts, co
     int rc = require_gpu(); if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
 
-    // ---- the tables: segments, the columns of every repeat, chunks (device segments first, then the host pieces slab by slab) ----
+    // ---- the tables: segments, the columns of every repeat ----
     std::vector<FSeg> segs((size_t)S);
     std::vector<int64_t> rep_cols(weights ? (size_t)R + 1 : 0, 0);
-    std::vector<FChunk> chunks;
-    chunks.reserve((size_t)nchunks);
-    std::vector<char> device((size_t)S);
+    std::vector<char> device((size_t)S), staged((size_t)S);
+    std::vector<size_t> row_bytes((size_t)S);
     int64_t npart = 0;
     {
         int64_t col = 0;
@@ -441,93 +415,48 @@ extern "C" int bluest_field_sums(int64_t S, int64_t d, const int64_t *counts, co
             npart += nc * W;
             if (weights) rep_cols[repeat_of[s] + 1] = col;              // repeat_of does not decrease: the last segment of a repeat wins
             device[s] = counts[s] > 0 && on_device(values[s]);
+            staged[s] = counts[s] > 0 && !device[s];
+            row_bytes[s] = (size_t)W * 8;
         }
         for (size_t r = 1; r < rep_cols.size(); r++) rep_cols[r] = std::max(rep_cols[r], rep_cols[r - 1]);   // a repeat without segments
     }
-    auto add_chunks = [&](int64_t s, const double *base, int64_t first, int64_t rows) {
-        const int64_t W = segs[s].W;
-        for (int64_t a = 0; a < rows; a += GCHUNK)
-            chunks.push_back(FChunk{base + a * W, segs[s].part + ((first + a) / GCHUNK) * W, W, (int32_t)std::min<int64_t>(GCHUNK, rows - a)});
-    };
-    for (int64_t s = 0; s < S; s++)
-        if (device[s]) add_chunks(s, values[s], 0, counts[s]);
-    const size_t n_device_chunks = chunks.size();
+    const SlabPlan plan = plan_slabs(S, counts, row_bytes.data(), staged.data(), GCHUNK, (size_t)slab_budget());
 
-    // slabs of the staging buffer: whole chunks only, each piece 256-byte aligned; a slab holds at least one chunk
-    const size_t budget = std::max<size_t>((size_t)slab_budget(), (size_t)GCHUNK * Lmax * d * 8 + 256);
-    std::vector<Piece> pieces;
-    std::vector<size_t> slab_used;
-    {
-        size_t used = 0;
-        int slab = 0;
-        bool open = false;
-        for (int64_t s = 0; s < S; s++) {
-            if (device[s] || counts[s] == 0) continue;
-            const size_t row_bytes = (size_t)segs[s].W * 8;
-            int64_t a = 0;
-            while (a < counts[s]) {
-                const int64_t rest = counts[s] - a;
-                int64_t fit = (int64_t)((budget - used) / row_bytes);
-                if (fit < rest) fit -= fit % GCHUNK;
-                if (fit <= 0) {                 // (an empty slab always fits a chunk: budget >= the widest chunk)
-                    slab_used.push_back(used);
-                    slab++;
-                    used = 0;
-                    continue;
-                }
-                const int64_t rows = std::min(rest, fit);
-                pieces.push_back(Piece{s, a, rows, used, slab});
-                used = std::min(budget, (used + (size_t)rows * row_bytes + 255) & ~(size_t)255);
-                open = true;
-                a += rows;
-            }
-        }
-        if (open) slab_used.push_back(used);
-    }
-    const size_t stage_bytes = slab_used.empty() ? 0 : *std::max_element(slab_used.begin(), slab_used.end());
-
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    DeviceArena arena;
     const size_t vec = (size_t)T * d * 8;
-    const size_t o_stage = take(stage_bytes + 256), o_part = take((size_t)npart * 8), o_chunks = take((size_t)nchunks * sizeof(FChunk)),
-                 o_segs = take((size_t)S * sizeof(FSeg)), o_sums = take(vec), o_w = take(weights ? (size_t)T * 8 : 0),
-                 o_rc = take(rep_cols.size() * 8), o_mu = take(weights ? (size_t)R * d * 8 : 0);
-    char *dv = nullptr;
-    HIP_TRY(hipMalloc(&dv, off));
-    struct Free { char *p; ~Free() { if (p) (void)hipFree(p); } } guard{dv};
+    const size_t o_stage = arena.take(plan.stage_bytes + 256), o_part = arena.take((size_t)npart * 8),
+                 o_chunks = arena.take((size_t)nchunks * sizeof(FChunk)), o_segs = arena.take((size_t)S * sizeof(FSeg)), o_sums = arena.take(vec),
+                 o_w = arena.take(weights ? (size_t)T * 8 : 0), o_rc = arena.take(rep_cols.size() * 8),
+                 o_mu = arena.take(weights ? (size_t)R * d * 8 : 0);
+    HIP_TRY(arena.alloc());
+    char *dv = arena.base;
     const double *d_stage = (const double *)(dv + o_stage);
     double *d_part = (double *)(dv + o_part), *d_sums = (double *)(dv + o_sums);
     FChunk *d_chunks = (FChunk *)(dv + o_chunks);
 
-    // the chunk table of every slab is known before anything is copied: one upload
-    std::vector<size_t> slab_chunk0;
-    for (size_t p = 0; p < pieces.size(); p++) {
-        if (p == 0 || pieces[p].slab != pieces[p - 1].slab) slab_chunk0.push_back(chunks.size());
-        const Piece &pc = pieces[p];
-        add_chunks(pc.seg, d_stage + pc.at / 8, pc.first, pc.rows);
-    }
-    slab_chunk0.push_back(chunks.size());
-    if ((int64_t)chunks.size() != nchunks) return fail(BLUEST_ERR_HIP, "internal: %zu chunks tabled, %lld expected", chunks.size(), (long long)nchunks);
-    if (nchunks > 0) HIP_TRY(hipMemcpyAsync(d_chunks, chunks.data(), (size_t)nchunks * sizeof(FChunk), hipMemcpyHostToDevice, st));
+    // ---- the chunks: launch group 0 reads the device segments where they lie, group 1 + k the pieces of slab k ----
+    ChunkLists<FChunk> chunks(1 + plan.slab_used.size(), 1, nchunks);
+    auto add_chunks = [&](size_t g, int64_t s, const double *base, int64_t first, int64_t rows) {
+        const int64_t W = segs[s].W;
+        for (int64_t a = 0; a < rows; a += GCHUNK)
+            chunks.add(g, 0, FChunk{base + a * W, segs[s].part + ((first + a) / GCHUNK) * W, W, (int32_t)std::min<int64_t>(GCHUNK, rows - a)});
+    };
+    for (int64_t s = 0; s < S; s++)
+        if (device[s]) add_chunks(0, s, values[s], 0, counts[s]);
+    for (const Piece &pc : plan.pieces) add_chunks(1 + (size_t)pc.slab, pc.seg, d_stage + pc.at / 8, pc.first, pc.rows);
+    rc = chunks.flatten(); if (rc) return rc;
+    if (nchunks > 0) HIP_TRY(hipMemcpyAsync(d_chunks, chunks.table.data(), (size_t)nchunks * sizeof(FChunk), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dv + o_segs, segs.data(), (size_t)S * sizeof(FSeg), hipMemcpyHostToDevice, st));
 
     const int64_t Wmax = (int64_t)Lmax * d;
-    auto launch_partial = [&](size_t c0, size_t c1) -> hipError_t {
+    auto launch_group = [&](size_t g) -> hipError_t {
+        const size_t c0 = chunks.begin(g), c1 = chunks.end(g);
         if (c1 <= c0) return hipSuccess;
         const dim3 grid((unsigned)(c1 - c0), (unsigned)std::min<int64_t>((Wmax + BLK - 1) / BLK, 65535));
         hipLaunchKernelGGL(k_fsum_partial, grid, dim3(BLK), 0, st, (const FChunk *)d_chunks + c0, d_part);
         return hipGetLastError();
     };
-    HIP_TRY(launch_partial(0, n_device_chunks));
-    for (size_t p = 0, k = 0; p < pieces.size(); k++) {
-        const int slab = pieces[p].slab;
-        for (; p < pieces.size() && pieces[p].slab == slab; p++) {
-            const Piece &pc = pieces[p];
-            const int64_t W = segs[pc.seg].W;
-            HIP_TRY(hipMemcpyAsync(dv + o_stage + pc.at, values[pc.seg] + pc.first * W, (size_t)pc.rows * W * 8, hipMemcpyHostToDevice, st));
-        }
-        HIP_TRY(launch_partial(slab_chunk0[k], slab_chunk0[k + 1]));      // in stream order: the next slab's copies wait for it
-    }
+    rc = run_slabs(plan, dv + o_stage, values, counts, row_bytes.data(), 1, launch_group, st); if (rc) return rc;
     const dim3 gf((unsigned)S, (unsigned)std::min<int64_t>((Wmax + FOLD_COLS - 1) / FOLD_COLS, 65535));
     hipLaunchKernelGGL(k_fsum_fold, gf, dim3(BLK), 0, st, (const FSeg *)(dv + o_segs), (const double *)d_part, d_sums);
     HIP_TRY(hipGetLastError());

@@ -11,17 +11,13 @@
 //   k_gsum_fold     grid (fold group, output), fold group = one segment, or with weights all segments of one repeat: a wave per
 //                   column, lane l adds the chunks l, l + 64, ... in ascending order, the lanes are joined by a fixed tree; with
 //                   weights one thread then walks the group's columns in ascending order with fma.
-// Host segments are copied into one staging buffer slab by slab, every slab a whole number of chunks; the chunks' partial sums
-// all land in one buffer that the single fold reads, so a slab boundary never shows in the result.
+// The segments' checks, the slabs of staged host data, the chunk table and the slab loop are those of staging.hpp.
 #include "staging.hpp"
 
 namespace {
 
 constexpr int BLK = 256;
-constexpr int CHUNK = BLUEST_GSUM_CHUNK;
-constexpr int CLASSES = 8, CLASS_ROWS = CHUNK / CLASSES;
-static_assert(CLASSES * CLASS_ROWS == CHUNK, "the row classes tile the chunk");
-static_assert((size_t)CHUNK * BLUEST_MAX_MODELS * sizeof(double) <= 64 * 1024, "the staged chunk must fit the default LDS limit");
+static_assert((size_t)GCHUNK * BLUEST_MAX_MODELS * sizeof(double) <= 64 * 1024, "the staged chunk must fit the default LDS limit");
 static_assert(CLASSES * BLUEST_MAX_MODELS <= 2 * BLK, "at most two (class, column) sums per thread");
 
 std::atomic<int64_t> g_slab_bytes{BLUEST_GSUM_SLAB_BYTES};
@@ -85,11 +81,7 @@ __global__ __launch_bounds__(BLK) void k_gsum_partial(const GChunk *__restrict__
         if (p < CLASSES * L) tile[p] = q[h];
     }
     __syncthreads();
-    if (tid < L) {
-        const double *c = tile + tid;
-        const double s = ((c[0] + c[L]) + (c[2 * L] + c[3 * L])) + ((c[4 * L] + c[5 * L]) + (c[6 * L] + c[7 * L]));
-        part[d.part + o * L + tid] = s;
-    }
+    if (tid < L) part[d.part + o * L + tid] = class_tree(tile + tid, L);
 }
 
 __global__ __launch_bounds__(BLK) void k_gsum_fold(const GFold *__restrict__ folds, const GSeg *__restrict__ segs,
@@ -120,12 +112,6 @@ __global__ __launch_bounds__(BLK) void k_gsum_fold(const GFold *__restrict__ fol
     }
 }
 
-struct Piece {              // rows [first, first + rows) of a host segment, staged as [n_out][rows][L] at `at` bytes of its slab
-    int64_t seg, first, rows;
-    size_t at;
-    int slab;
-};
-
 }  // namespace
 
 extern "C" int bluest_group_sums_slab(int64_t bytes, int64_t *previous)
@@ -148,38 +134,28 @@ extern "C" int bluest_group_sums(int64_t S, int n_out, const int64_t *counts, co
     int64_t T = 0, nchunks = 0, npart = 0;
     int Lmax = 1;
     for (int64_t s = 0; s < S; s++) {
-        if (sizes[s] < 1 || sizes[s] > BLUEST_MAX_MODELS)
-            return fail(BLUEST_ERR_ARG, "sizes[%lld]=%d out of range (1..%d)", (long long)s, sizes[s], BLUEST_MAX_MODELS);
-        if (counts[s] < 0) return fail(BLUEST_ERR_ARG, "counts[%lld]=%lld is negative", (long long)s, (long long)counts[s]);
-        if (counts[s] > 0 && !values[s]) return fail(BLUEST_ERR_ARG, "values[%lld] is null", (long long)s);
-        if (counts[s] > 0 && ((uintptr_t)values[s] & 7)) return fail(BLUEST_ERR_ARG, "values[%lld] is not 8-byte aligned", (long long)s);
-        if (weights) {
-            if (repeat_of[s] < 0 || repeat_of[s] >= R)
-                return fail(BLUEST_ERR_ARG, "repeat_of[%lld]=%lld out of range (0..%d)", (long long)s, (long long)repeat_of[s], R - 1);
-            if (s > 0 && repeat_of[s] < repeat_of[s - 1]) return fail(BLUEST_ERR_ARG, "repeat_of decreases at segment %lld", (long long)s);
-        }
-        const int64_t nc = (counts[s] + CHUNK - 1) / CHUNK;
+        int rc = check_segment(s, counts, sizes, values, weights ? repeat_of : nullptr, R); if (rc) return rc;
+        const int64_t nc = (counts[s] + GCHUNK - 1) / GCHUNK;
         T += sizes[s];
         nchunks += nc;
         npart += nc * n_out * sizes[s];
         Lmax = std::max(Lmax, (int)sizes[s]);
     }
     if (T > 0x7fffffffLL || nchunks > 0x7fffffffLL)
-        return fail(BLUEST_ERR_ARG, "more than 2^31 - 1 columns or chunks of %d samples in one call", CHUNK);
+        return fail(BLUEST_ERR_ARG, "more than 2^31 - 1 columns or chunks of %d samples in one call", GCHUNK);
     int rc = require_gpu(); if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
 
-    // ---- the tables: segments, columns, fold groups, chunks (device segments first, then the host pieces slab by slab) ----
+    // ---- the tables: segments, columns, fold groups ----
     std::vector<GSeg> segs((size_t)S);
     std::vector<int32_t> col_seg((size_t)T);
     std::vector<GFold> folds;
-    std::vector<GChunk> chunks;
-    chunks.reserve((size_t)nchunks);
-    std::vector<char> device((size_t)S);
+    std::vector<char> device((size_t)S), staged((size_t)S);
+    std::vector<size_t> row_bytes((size_t)S);       // a row of a staged piece: [n_out][L]
     {
         int64_t col = 0, part = 0;
         for (int64_t s = 0; s < S; s++) {
-            const int64_t nc = (counts[s] + CHUNK - 1) / CHUNK;
+            const int64_t nc = (counts[s] + GCHUNK - 1) / GCHUNK;
             segs[s] = GSeg{part, nc, sizes[s], (int32_t)col};
             for (int j = 0; j < sizes[s]; j++) col_seg[col + j] = (int32_t)s;
             if (weights && !folds.empty() && folds.back().repeat == repeat_of[s]) folds.back().col1 = col + sizes[s];
@@ -187,75 +163,39 @@ extern "C" int bluest_group_sums(int64_t S, int n_out, const int64_t *counts, co
             col += sizes[s];
             part += nc * n_out * sizes[s];
             device[s] = counts[s] > 0 && on_device(values[s]);
+            staged[s] = counts[s] > 0 && !device[s];
+            row_bytes[s] = (size_t)sizes[s] * 8 * n_out;
         }
     }
-    auto add_chunks = [&](int64_t s, const double *base, int64_t first, int64_t rows, int64_t ostride) {
-        const int L = sizes[s];
-        for (int64_t a = 0; a < rows; a += CHUNK)
-            chunks.push_back(GChunk{base + a * L, ostride, segs[s].part + ((first + a) / CHUNK) * n_out * L,
-                                    (int32_t)std::min<int64_t>(CHUNK, rows - a), L});
-    };
-    for (int64_t s = 0; s < S; s++)
-        if (device[s]) add_chunks(s, values[s], 0, counts[s], counts[s] * sizes[s]);
-    const size_t n_device_chunks = chunks.size();
+    const SlabPlan plan = plan_slabs(S, counts, row_bytes.data(), staged.data(), GCHUNK, (size_t)slab_budget());
 
-    // slabs of the staging buffer: whole chunks only, each piece 256-byte aligned; a slab holds at least one chunk
-    const size_t budget = std::max<size_t>((size_t)g_slab_bytes.load(), (size_t)CHUNK * Lmax * 8 * n_out + 256);
-    std::vector<Piece> pieces;
-    std::vector<size_t> slab_used;              // bytes per slab
-    {
-        size_t used = 0;
-        int slab = 0;
-        bool open = false;
-        for (int64_t s = 0; s < S; s++) {
-            if (device[s] || counts[s] == 0) continue;
-            const size_t row_bytes = (size_t)sizes[s] * 8 * n_out;
-            int64_t a = 0;
-            while (a < counts[s]) {
-                const int64_t rest = counts[s] - a;
-                int64_t fit = (int64_t)((budget - used) / row_bytes);
-                if (fit < rest) fit -= fit % CHUNK;
-                if (fit <= 0) {                 // (an empty slab always fits a chunk: budget >= the widest chunk)
-                    slab_used.push_back(used);
-                    slab++;
-                    used = 0;
-                    continue;
-                }
-                const int64_t rows = std::min(rest, fit);
-                pieces.push_back(Piece{s, a, rows, used, slab});
-                used = std::min(budget, (used + (size_t)rows * row_bytes + 255) & ~(size_t)255);
-                open = true;
-                a += rows;
-            }
-        }
-        if (open) slab_used.push_back(used);
-    }
-    const size_t stage_bytes = slab_used.empty() ? 0 : *std::max_element(slab_used.begin(), slab_used.end());
-
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    DeviceArena arena;
     const size_t vec = (size_t)n_out * T * 8;
-    const size_t o_stage = take(stage_bytes + 256), o_part = take((size_t)npart * 8), o_chunks = take((size_t)nchunks * sizeof(GChunk)),
-                 o_segs = take((size_t)S * sizeof(GSeg)), o_cols = take((size_t)T * 4), o_folds = take(folds.size() * sizeof(GFold)),
-                 o_sums = take(vec), o_w = take(weights ? vec : 0), o_mu = take(weights ? (size_t)R * n_out * 8 : 0);
-    char *dv = nullptr;
-    HIP_TRY(hipMalloc(&dv, off));
-    struct Free { char *p; ~Free() { if (p) (void)hipFree(p); } } guard{dv};
+    const size_t o_stage = arena.take(plan.stage_bytes + 256), o_part = arena.take((size_t)npart * 8),
+                 o_chunks = arena.take((size_t)nchunks * sizeof(GChunk)), o_segs = arena.take((size_t)S * sizeof(GSeg)),
+                 o_cols = arena.take((size_t)T * 4), o_folds = arena.take(folds.size() * sizeof(GFold)), o_sums = arena.take(vec),
+                 o_w = arena.take(weights ? vec : 0), o_mu = arena.take(weights ? (size_t)R * n_out * 8 : 0);
+    HIP_TRY(arena.alloc());
+    char *dv = arena.base;
     const double *d_stage = (const double *)(dv + o_stage);
     double *d_part = (double *)(dv + o_part), *d_sums = (double *)(dv + o_sums);
     double *d_w = weights ? (double *)(dv + o_w) : nullptr, *d_mu = weights ? (double *)(dv + o_mu) : nullptr;
     GChunk *d_chunks = (GChunk *)(dv + o_chunks);
 
-    // the chunk table of every slab is known before anything is copied: one upload
-    std::vector<size_t> slab_chunk0;
-    for (size_t p = 0; p < pieces.size(); p++) {
-        if (p == 0 || pieces[p].slab != pieces[p - 1].slab) slab_chunk0.push_back(chunks.size());
-        const Piece &pc = pieces[p];
-        add_chunks(pc.seg, d_stage + pc.at / 8, pc.first, pc.rows, pc.rows * sizes[pc.seg]);
-    }
-    slab_chunk0.push_back(chunks.size());
-    if ((int64_t)chunks.size() != nchunks) return fail(BLUEST_ERR_HIP, "internal: %zu chunks tabled, %lld expected", chunks.size(), (long long)nchunks);
-    if (nchunks > 0) HIP_TRY(hipMemcpyAsync(d_chunks, chunks.data(), (size_t)nchunks * sizeof(GChunk), hipMemcpyHostToDevice, st));
+    // ---- the chunks: launch group 0 reads the device segments where they lie, group 1 + k the pieces of slab k ----
+    ChunkLists<GChunk> chunks(1 + plan.slab_used.size(), 1, nchunks);
+    auto add_chunks = [&](size_t g, int64_t s, const double *base, int64_t first, int64_t rows, int64_t ostride) {
+        const int L = sizes[s];
+        for (int64_t a = 0; a < rows; a += GCHUNK)
+            chunks.add(g, 0, GChunk{base + a * L, ostride, segs[s].part + ((first + a) / GCHUNK) * n_out * L,
+                                    (int32_t)std::min<int64_t>(GCHUNK, rows - a), L});
+    };
+    for (int64_t s = 0; s < S; s++)
+        if (device[s]) add_chunks(0, s, values[s], 0, counts[s], counts[s] * sizes[s]);
+    for (const Piece &pc : plan.pieces)
+        add_chunks(1 + (size_t)pc.slab, pc.seg, d_stage + pc.at / 8, pc.first, pc.rows, pc.rows * sizes[pc.seg]);
+    rc = chunks.flatten(); if (rc) return rc;
+    if (nchunks > 0) HIP_TRY(hipMemcpyAsync(d_chunks, chunks.table.data(), (size_t)nchunks * sizeof(GChunk), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dv + o_segs, segs.data(), (size_t)S * sizeof(GSeg), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dv + o_cols, col_seg.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dv + o_folds, folds.data(), folds.size() * sizeof(GFold), hipMemcpyHostToDevice, st));
@@ -264,30 +204,15 @@ extern "C" int bluest_group_sums(int64_t S, int n_out, const int64_t *counts, co
         HIP_TRY(hipMemsetAsync(d_mu, 0, (size_t)R * n_out * 8, st));
     }
 
-    const size_t lds = (size_t)CHUNK * Lmax * 8;
-    auto launch_partial = [&](size_t c0, size_t c1) -> hipError_t {
+    const size_t lds = (size_t)GCHUNK * Lmax * 8;
+    auto launch_group = [&](size_t g) -> hipError_t {
+        const size_t c0 = chunks.begin(g), c1 = chunks.end(g);
         if (c1 <= c0) return hipSuccess;
         hipLaunchKernelGGL(k_gsum_partial, dim3((unsigned)(c1 - c0), (unsigned)n_out), dim3(BLK), lds, st,
                            (const GChunk *)d_chunks + c0, d_part);
         return hipGetLastError();
     };
-    HIP_TRY(launch_partial(0, n_device_chunks));
-    for (size_t p = 0, k = 0; p < pieces.size(); k++) {
-        const int slab = pieces[p].slab;
-        for (; p < pieces.size() && pieces[p].slab == slab; p++) {
-            const Piece &pc = pieces[p];
-            const int64_t L = sizes[pc.seg], N = counts[pc.seg];
-            char *dst = dv + o_stage + pc.at;
-            if (pc.rows == N) {
-                HIP_TRY(hipMemcpyAsync(dst, values[pc.seg], (size_t)n_out * N * L * 8, hipMemcpyHostToDevice, st));
-            } else {
-                for (int o = 0; o < n_out; o++)
-                    HIP_TRY(hipMemcpyAsync(dst + (size_t)o * pc.rows * L * 8, values[pc.seg] + ((int64_t)o * N + pc.first) * L,
-                                           (size_t)pc.rows * L * 8, hipMemcpyHostToDevice, st));
-            }
-        }
-        HIP_TRY(launch_partial(slab_chunk0[k], slab_chunk0[k + 1]));      // in stream order: the next slab's copies wait for it
-    }
+    rc = run_slabs(plan, dv + o_stage, values, counts, row_bytes.data(), n_out, launch_group, st); if (rc) return rc;
     hipLaunchKernelGGL(k_gsum_fold, dim3((unsigned)folds.size(), (unsigned)n_out), dim3(BLK), 0, st, (const GFold *)(dv + o_folds),
                        (const GSeg *)(dv + o_segs), (const int32_t *)(dv + o_cols), n_out, T, (const double *)d_part,
                        (const double *)d_w, d_sums, d_mu);

@@ -1,8 +1,9 @@
 // moments.hip -- Part 13 of include/bluest_hip.h: first and second moments about the first sample of many ragged segments in one
 // call (the sample covariance of every drawn model group: what gsums.hip adds up and throws away).
 //
-// The segments, the chunk table, the slabs of staged host data and the fold are those of gsums.hip; what is new is the work of a
-// chunk.  Per call one k_mom_* launch per (slab, kernel shape) and one k_mom_fold, no atomics, nothing sized by the device:
+// The segments, the chunk table and the slabs of staged host data are those of staging.hpp, the fold is that of gsums.hip; what
+// is its own is the work of a chunk.  Per call one k_mom_* launch per (slab, kernel shape) and one k_mom_fold, no atomics, nothing
+// sized by the device:
 //   k_mom_narrow / k_mom_wide  grid (chunk, output): stages the chunk's rows x L values in LDS as gsums.hip does (16-byte loads
 //                   from the first 16-byte boundary on), SUBTRACTING THE SEGMENT'S FIRST SAMPLE on the way (one rounding per
 //                   value), and fills the rows up to the next multiple of 16 with +0.0.  An ENTRY of a segment is one of its L
@@ -17,24 +18,21 @@
 //   5 <= L <= 22  k_mom_narrow<256>   a thread per (class, entry), at most 8 * 275 = 2200: nine passes; the class sums wait in
 //                                     registers until every read of the tile is done, then go where the tile was (8 (L + P) <= 128 L)
 //   L >= 23       k_mom_wide          a thread per entry (299 .. 2144 of them) with its eight class sums in registers
-// Host segments are staged slab by slab exactly as in gsums.hip; the first-sample rows of all host segments travel in a buffer of
+// Host segments are staged slab by slab (staging.hpp); the first-sample rows of all host segments travel in a buffer of
 // their own, so a chunk in a later slab still finds its segment's shift.
 #include "staging.hpp"
 
 namespace {
 
 constexpr int BLK = 256;
-constexpr int CHUNK = BLUEST_GSUM_CHUNK;
-constexpr int CLASSES = 8, CLASS_ROWS = CHUNK / CLASSES;
 constexpr int NARROW_1WAVE = 4, NARROW_MAX = 22;             // the widest L of k_mom_narrow<64> and of k_mom_narrow<256>
-static_assert(CLASSES * CLASS_ROWS == CHUNK && CLASS_ROWS == 16, "the row classes tile the chunk");
-static_assert((size_t)CHUNK * BLUEST_MAX_MODELS * sizeof(double) <= 64 * 1024, "the staged chunk must fit the default LDS limit");
+static_assert((size_t)GCHUNK * BLUEST_MAX_MODELS * sizeof(double) <= 64 * 1024, "the staged chunk must fit the default LDS limit");
 
 __host__ __device__ constexpr int entries_of(int L) { return L + L * (L + 1) / 2; }
 constexpr int passes_of(int L, int blk) { return (CLASSES * entries_of(L) + blk - 1) / blk; }
 constexpr int NP_1WAVE = passes_of(NARROW_1WAVE, WAVE), NP_NARROW = passes_of(NARROW_MAX, BLK);
-static_assert(CLASSES * entries_of(NARROW_MAX) <= CHUNK * NARROW_MAX, "the class sums of a narrow chunk fit where its tile was");
-static_assert(CLASSES * entries_of(NARROW_1WAVE) <= CHUNK * NARROW_1WAVE && CLASSES * entries_of(1) <= CHUNK, "and at every narrower L");
+static_assert(CLASSES * entries_of(NARROW_MAX) <= GCHUNK * NARROW_MAX, "the class sums of a narrow chunk fit where its tile was");
+static_assert(CLASSES * entries_of(NARROW_1WAVE) <= GCHUNK * NARROW_1WAVE && CLASSES * entries_of(1) <= GCHUNK, "and at every narrower L");
 
 struct MChunk {
     const double *src;      // row 0 of the chunk, output 0 (device address)
@@ -125,10 +123,7 @@ __global__ __launch_bounds__(B) void k_mom_narrow(const MChunk *__restrict__ tab
         if (p < items) tile[p] = q[h];
     }
     __syncthreads();
-    for (int e = tid; e < W; e += B) {
-        const double *c = tile + e;
-        part[d.part + o * W + e] = ((c[0] + c[W]) + (c[2 * W] + c[3 * W])) + ((c[4 * W] + c[5 * W]) + (c[6 * W] + c[7 * W]));
-    }
+    for (int e = tid; e < W; e += B) part[d.part + o * W + e] = class_tree(tile + e, W);
 }
 
 __global__ __launch_bounds__(BLK) void k_mom_wide(const MChunk *__restrict__ table, double *__restrict__ part)
@@ -148,7 +143,7 @@ __global__ __launch_bounds__(BLK) void k_mom_wide(const MChunk *__restrict__ tab
             q[k] = 0.0;
             if (k < kcount) q[k] = class_sum(tile + k * CLASS_ROWS * L, L, e);
         }
-        part[d.part + o * W + e] = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
+        part[d.part + o * W + e] = class_tree(q);
     }
 }
 
@@ -176,12 +171,6 @@ __global__ __launch_bounds__(BLK) void k_mom_fold(const MSeg *__restrict__ segs,
     }
 }
 
-struct Piece {              // rows [first, first + rows) of a host segment, staged as [n_out][rows][L] at `at` bytes of its slab
-    int64_t seg, first, rows;
-    size_t at;
-    int slab;
-};
-
 enum { SHAPE_1WAVE = 0, SHAPE_NARROW = 1, SHAPE_WIDE = 2, SHAPES = 3 };
 int moments_shape(int L) { return L <= NARROW_1WAVE ? SHAPE_1WAVE : L <= NARROW_MAX ? SHAPE_NARROW : SHAPE_WIDE; }
 
@@ -195,40 +184,36 @@ extern "C" int bluest_group_moments(int64_t S, int n_out, const int64_t *counts,
         return fail(BLUEST_ERR_ARG, "n_out=%d out of range (1..%d)", n_out, BLUEST_GSUM_MAX_OUTPUTS);
     if (!counts || !sizes || !values || !first || !second) return fail(BLUEST_ERR_ARG, "null pointer");
     int64_t T = 0, P = 0, nchunks = 0, npart = 0;
-    int Lmax[SHAPES] = {0, 0, 0}, Lwidest = 1;
+    int Lmax[SHAPES] = {0, 0, 0};
     for (int64_t s = 0; s < S; s++) {
-        if (sizes[s] < 1 || sizes[s] > BLUEST_MAX_MODELS)
-            return fail(BLUEST_ERR_ARG, "sizes[%lld]=%d out of range (1..%d)", (long long)s, sizes[s], BLUEST_MAX_MODELS);
-        if (counts[s] < 0) return fail(BLUEST_ERR_ARG, "counts[%lld]=%lld is negative", (long long)s, (long long)counts[s]);
-        if (counts[s] > 0 && !values[s]) return fail(BLUEST_ERR_ARG, "values[%lld] is null", (long long)s);
-        if (counts[s] > 0 && ((uintptr_t)values[s] & 7)) return fail(BLUEST_ERR_ARG, "values[%lld] is not 8-byte aligned", (long long)s);
+        int rc = check_segment(s, counts, sizes, values); if (rc) return rc;
         const int L = sizes[s];
-        const int64_t nc = (counts[s] + CHUNK - 1) / CHUNK;
+        const int64_t nc = (counts[s] + GCHUNK - 1) / GCHUNK;
         T += L;
         P += L * (L + 1) / 2;
         nchunks += nc;
         npart += nc * n_out * entries_of(L);
         Lmax[moments_shape(L)] = std::max(Lmax[moments_shape(L)], L);
-        Lwidest = std::max(Lwidest, L);
     }
     if (T > 0x7fffffffLL || nchunks > 0x7fffffffLL)
-        return fail(BLUEST_ERR_ARG, "more than 2^31 - 1 columns or chunks of %d samples in one call", CHUNK);
+        return fail(BLUEST_ERR_ARG, "more than 2^31 - 1 columns or chunks of %d samples in one call", GCHUNK);
     if (P > 0x7fffffffLL) return fail(BLUEST_ERR_ARG, "more than 2^31 - 1 packed pairs in one call");
     int rc = require_gpu(); if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int64_t E = T + P;
 
-    // ---- the tables: segments, entries, chunks (per slab and kernel shape; device segments are "slab" 0, read in place) ----
+    // ---- the tables: segments, entries ----
     std::vector<MSeg> segs((size_t)S);
     std::vector<int32_t> ent_seg((size_t)E);
-    std::vector<char> device((size_t)S);
+    std::vector<char> device((size_t)S), staged((size_t)S);
+    std::vector<size_t> row_bytes((size_t)S);          // a row of a staged piece: [n_out][L]
     std::vector<int64_t> shift_at((size_t)S, -1);      // host segments: where the first-sample rows [n_out][L] lie in the shift buffer
     int64_t nshift = 0;
     {
         int64_t col = 0, pair = 0, part = 0, ent = 0;
         for (int64_t s = 0; s < S; s++) {
             const int L = sizes[s];
-            const int64_t nc = (counts[s] + CHUNK - 1) / CHUNK;
+            const int64_t nc = (counts[s] + GCHUNK - 1) / GCHUNK;
             segs[s] = MSeg{part, nc, ent, col, pair, L};
             std::fill(ent_seg.begin() + ent, ent_seg.begin() + ent + entries_of(L), (int32_t)s);
             col += L;
@@ -236,7 +221,9 @@ extern "C" int bluest_group_moments(int64_t S, int n_out, const int64_t *counts,
             ent += entries_of(L);
             part += nc * n_out * entries_of(L);
             device[s] = counts[s] > 0 && on_device(values[s]);
-            if (counts[s] > 0 && !device[s]) {
+            staged[s] = counts[s] > 0 && !device[s];
+            row_bytes[s] = (size_t)L * 8 * n_out;
+            if (staged[s]) {
                 shift_at[s] = nshift;
                 nshift += (int64_t)n_out * L;
             }
@@ -249,82 +236,37 @@ extern "C" int bluest_group_moments(int64_t S, int n_out, const int64_t *counts,
                 std::memcpy(shifts.data() + shift_at[s] + (int64_t)o * sizes[s], values[s] + (int64_t)o * counts[s] * sizes[s],
                             (size_t)sizes[s] * 8);
 
-    // slabs of the staging buffer: whole chunks only, each piece 256-byte aligned; a slab holds at least one chunk
-    int64_t slab_bytes = 0;
-    rc = bluest_group_sums_slab(0, &slab_bytes); if (rc) return rc;
-    const size_t budget = std::max<size_t>((size_t)slab_bytes, (size_t)CHUNK * Lwidest * 8 * n_out + 256);
-    std::vector<Piece> pieces;
-    std::vector<size_t> slab_used;              // bytes per slab
-    {
-        size_t used = 0;
-        int slab = 0;
-        bool open = false;
-        for (int64_t s = 0; s < S; s++) {
-            if (device[s] || counts[s] == 0) continue;
-            const size_t row_bytes = (size_t)sizes[s] * 8 * n_out;
-            int64_t a = 0;
-            while (a < counts[s]) {
-                const int64_t rest = counts[s] - a;
-                int64_t fit = (int64_t)((budget - used) / row_bytes);
-                if (fit < rest) fit -= fit % CHUNK;
-                if (fit <= 0) {                 // (an empty slab always fits a chunk: budget >= the widest chunk)
-                    slab_used.push_back(used);
-                    slab++;
-                    used = 0;
-                    continue;
-                }
-                const int64_t rows = std::min(rest, fit);
-                pieces.push_back(Piece{s, a, rows, used, slab});
-                used = std::min(budget, (used + (size_t)rows * row_bytes + 255) & ~(size_t)255);
-                open = true;
-                a += rows;
-            }
-        }
-        if (open) slab_used.push_back(used);
-    }
-    const size_t stage_bytes = slab_used.empty() ? 0 : *std::max_element(slab_used.begin(), slab_used.end());
-    const size_t n_slabs = slab_used.size();
+    const SlabPlan plan = plan_slabs(S, counts, row_bytes.data(), staged.data(), GCHUNK, (size_t)slab_budget());
 
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    DeviceArena arena;
     const size_t b_first = (size_t)n_out * T * 8, b_second = (size_t)n_out * P * 8;
-    const size_t o_stage = take(stage_bytes + 256), o_shift = take((size_t)nshift * 8), o_part = take((size_t)npart * 8),
-                 o_chunks = take((size_t)nchunks * sizeof(MChunk)), o_segs = take((size_t)S * sizeof(MSeg)),
-                 o_ents = take((size_t)E * 4), o_first = take(b_first), o_second = take(b_second);
-    char *dv = nullptr;
-    HIP_TRY(hipMalloc(&dv, off));
-    struct Free { char *p; ~Free() { if (p) (void)hipFree(p); } } guard{dv};
+    const size_t o_stage = arena.take(plan.stage_bytes + 256), o_shift = arena.take((size_t)nshift * 8), o_part = arena.take((size_t)npart * 8),
+                 o_chunks = arena.take((size_t)nchunks * sizeof(MChunk)), o_segs = arena.take((size_t)S * sizeof(MSeg)),
+                 o_ents = arena.take((size_t)E * 4), o_first = arena.take(b_first), o_second = arena.take(b_second);
+    HIP_TRY(arena.alloc());
+    char *dv = arena.base;
     const double *d_stage = (const double *)(dv + o_stage), *d_shift = (const double *)(dv + o_shift);
     double *d_part = (double *)(dv + o_part), *d_first = (double *)(dv + o_first), *d_second = (double *)(dv + o_second);
     MChunk *d_chunks = (MChunk *)(dv + o_chunks);
 
-    // the chunks of launch (g, shape), g = 0 for the device segments and 1 + slab for a slab, lie together in the table
-    std::vector<std::vector<MChunk>> lists((1 + n_slabs) * SHAPES);
+    // ---- the chunks: launch group 0 reads the device segments where they lie, group 1 + k the pieces of slab k; a list per shape ----
+    ChunkLists<MChunk> chunks(1 + plan.slab_used.size(), SHAPES, nchunks);
     auto add_chunks = [&](size_t g, int64_t s, const double *base, int64_t first_row, int64_t rows, int64_t ostride,
                           const double *shift, int64_t sstride) {
         const int L = sizes[s], W = entries_of(L);
-        std::vector<MChunk> &list = lists[g * SHAPES + moments_shape(L)];
-        for (int64_t a = 0; a < rows; a += CHUNK)
-            list.push_back(MChunk{base + a * L, shift, ostride, sstride, segs[s].part + ((first_row + a) / CHUNK) * n_out * W,
-                                  (int32_t)std::min<int64_t>(CHUNK, rows - a), L});
+        for (int64_t a = 0; a < rows; a += GCHUNK)
+            chunks.add(g, moments_shape(L), MChunk{base + a * L, shift, ostride, sstride, segs[s].part + ((first_row + a) / GCHUNK) * n_out * W,
+                                                   (int32_t)std::min<int64_t>(GCHUNK, rows - a), L});
     };
     for (int64_t s = 0; s < S; s++)
         if (device[s]) add_chunks(0, s, values[s], 0, counts[s], counts[s] * sizes[s], values[s], counts[s] * sizes[s]);
-    for (const Piece &pc : pieces)
+    for (const Piece &pc : plan.pieces)
         add_chunks(1 + (size_t)pc.slab, pc.seg, d_stage + pc.at / 8, pc.first, pc.rows, pc.rows * sizes[pc.seg],
                    d_shift + shift_at[pc.seg], sizes[pc.seg]);
-    std::vector<MChunk> chunks;
-    chunks.reserve((size_t)nchunks);
-    std::vector<size_t> list0(lists.size() + 1);
-    for (size_t i = 0; i < lists.size(); i++) {
-        list0[i] = chunks.size();
-        chunks.insert(chunks.end(), lists[i].begin(), lists[i].end());
-    }
-    list0[lists.size()] = chunks.size();
-    if ((int64_t)chunks.size() != nchunks) return fail(BLUEST_ERR_HIP, "internal: %zu chunks tabled, %lld expected", chunks.size(), (long long)nchunks);
+    rc = chunks.flatten(); if (rc) return rc;
     // the tables lie side by side on the device: one image of them on the host, one copy
     std::vector<char> tables(o_first - o_chunks);
-    if (nchunks > 0) std::memcpy(tables.data(), chunks.data(), (size_t)nchunks * sizeof(MChunk));
+    if (nchunks > 0) std::memcpy(tables.data(), chunks.table.data(), (size_t)nchunks * sizeof(MChunk));
     std::memcpy(tables.data() + (o_segs - o_chunks), segs.data(), (size_t)S * sizeof(MSeg));
     std::memcpy(tables.data() + (o_ents - o_chunks), ent_seg.data(), (size_t)E * 4);
     HIP_TRY(hipMemcpyAsync(dv + o_chunks, tables.data(), tables.size(), hipMemcpyHostToDevice, st));
@@ -332,10 +274,10 @@ extern "C" int bluest_group_moments(int64_t S, int n_out, const int64_t *counts,
 
     auto launch_group = [&](size_t g) -> hipError_t {
         for (int shape = 0; shape < SHAPES; shape++) {
-            const size_t c0 = list0[g * SHAPES + shape], c1 = list0[g * SHAPES + shape + 1];
+            const size_t c0 = chunks.begin(g, shape), c1 = chunks.end(g, shape);
             if (c1 <= c0) continue;
             const dim3 grid((unsigned)(c1 - c0), (unsigned)n_out);
-            const size_t lds = (size_t)CHUNK * Lmax[shape] * 8;
+            const size_t lds = (size_t)GCHUNK * Lmax[shape] * 8;
             const MChunk *table = d_chunks + c0;
             if (shape == SHAPE_1WAVE) hipLaunchKernelGGL((k_mom_narrow<WAVE, NP_1WAVE>), grid, dim3(WAVE), lds, st, table, d_part);
             else if (shape == SHAPE_NARROW) hipLaunchKernelGGL((k_mom_narrow<BLK, NP_NARROW>), grid, dim3(BLK), lds, st, table, d_part);
@@ -345,23 +287,7 @@ extern "C" int bluest_group_moments(int64_t S, int n_out, const int64_t *counts,
         }
         return hipSuccess;
     };
-    HIP_TRY(launch_group(0));
-    for (size_t p = 0; p < pieces.size();) {
-        const int slab = pieces[p].slab;
-        for (; p < pieces.size() && pieces[p].slab == slab; p++) {
-            const Piece &pc = pieces[p];
-            const int64_t L = sizes[pc.seg], N = counts[pc.seg];
-            char *dst = dv + o_stage + pc.at;
-            if (pc.rows == N) {
-                HIP_TRY(hipMemcpyAsync(dst, values[pc.seg], (size_t)n_out * N * L * 8, hipMemcpyHostToDevice, st));
-            } else {
-                for (int o = 0; o < n_out; o++)
-                    HIP_TRY(hipMemcpyAsync(dst + (size_t)o * pc.rows * L * 8, values[pc.seg] + ((int64_t)o * N + pc.first) * L,
-                                           (size_t)pc.rows * L * 8, hipMemcpyHostToDevice, st));
-            }
-        }
-        HIP_TRY(launch_group(1 + (size_t)slab));                          // in stream order: the next slab's copies wait for it
-    }
+    rc = run_slabs(plan, dv + o_stage, values, counts, row_bytes.data(), n_out, launch_group, st); if (rc) return rc;
     hipLaunchKernelGGL(k_mom_fold, dim3((unsigned)((E + BLK / WAVE - 1) / (BLK / WAVE)), (unsigned)n_out), dim3(BLK), 0, st,
                        (const MSeg *)(dv + o_segs), (const int32_t *)(dv + o_ents), E, n_out, T, P, (const double *)d_part, d_first,
                        d_second);

@@ -130,14 +130,12 @@ extern "C" int bluest_pilot_stats(int64_t N, int L, int n_out, const double *val
     const bool diff = sumsd1 != nullptr, staged = !on_device(values);
     const int npairs = n_pairs(L), ns = diff ? 3 : 1;
     const size_t in_bytes = (size_t)n_out * (size_t)N * L * 8, mat = (size_t)n_out * L * L * 8, vec = (size_t)n_out * L * 8;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_in = take(staged ? in_bytes : 0), o_part = take((size_t)n_out * nchunks * ns * npairs * 8),
-                 o_pe = take((size_t)n_out * nchunks * L * 8), o_se = take(vec), o_sc = take(mat), o_d1 = take(diff ? mat : 0),
-                 o_d2 = take(diff ? mat : 0);
-    char *dv = nullptr;
-    HIP_TRY(hipMalloc(&dv, off));
-    struct Free { char *p; ~Free() { if (p) (void)hipFree(p); } } guard{dv};
+    DeviceArena arena;
+    const size_t o_in = arena.take(staged ? in_bytes : 0), o_part = arena.take((size_t)n_out * nchunks * ns * npairs * 8),
+                 o_pe = arena.take((size_t)n_out * nchunks * L * 8), o_se = arena.take(vec), o_sc = arena.take(mat),
+                 o_d1 = arena.take(diff ? mat : 0), o_d2 = arena.take(diff ? mat : 0);
+    HIP_TRY(arena.alloc());
+    char *dv = arena.base;
     const double *d_in = values;
     if (staged) {
         HIP_TRY(hipMemcpyAsync(dv + o_in, values, in_bytes, hipMemcpyHostToDevice, st));

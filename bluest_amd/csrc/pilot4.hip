@@ -146,15 +146,14 @@ extern "C" int bluest_pilot_moments4(int64_t N, int L, int n_out, const double *
     const bool diff = tpow != nullptr, staged = !on_device(values);
     const int npairs = n_pairs(L);
     const size_t in_bytes = (size_t)n_out * (size_t)N * L * 8, mat = (size_t)n_out * L * L * 8, vec = (size_t)n_out * L * 8;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    DeviceArena arena;
     const int nsl = diff ? 2 * NS : NS;
-    const size_t o_in = take(staged ? in_bytes : 0), o_sh = take(shift ? vec : 0),
-                 o_part = take((size_t)n_out * nchunks * nsl * npairs * 8), o_pe = take((size_t)n_out * nchunks * L * 8),
-                 o_first = take(vec), o_11 = take(mat), o_21 = take(mat), o_22 = take(mat), o_tp = take(diff ? NS * mat : 0);
-    char *dv = nullptr;
-    HIP_TRY(hipMalloc(&dv, off));
-    struct Free { char *p; ~Free() { if (p) (void)hipFree(p); } } guard{dv};
+    const size_t o_in = arena.take(staged ? in_bytes : 0), o_sh = arena.take(shift ? vec : 0),
+                 o_part = arena.take((size_t)n_out * nchunks * nsl * npairs * 8), o_pe = arena.take((size_t)n_out * nchunks * L * 8),
+                 o_first = arena.take(vec), o_11 = arena.take(mat), o_21 = arena.take(mat), o_22 = arena.take(mat),
+                 o_tp = arena.take(diff ? NS * mat : 0);
+    HIP_TRY(arena.alloc());
+    char *dv = arena.base;
     const double *d_in = values;
     if (staged) {
         HIP_TRY(hipMemcpyAsync(dv + o_in, values, in_bytes, hipMemcpyHostToDevice, st));

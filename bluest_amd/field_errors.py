@@ -62,14 +62,9 @@ def field_weighted_moments(values, coef, slab_bytes=SLAB_BYTES):
     if not np.all(np.isfinite(coef)):
         raise ValueError("coef must be finite")
     zsum, zsq = np.empty((S, d)), np.empty((S, d))
-    lib = _lib.lib()
-    before = ctypes.c_int64(0)
-    _lib.check(lib.bluest_group_sums_slab(max(int(slab_bytes), 1), ctypes.byref(before)))
-    try:
-        _lib.check(lib.bluest_field_weighted_moments(S, d, _lib.ptr(counts), _lib.ptr(sizes), ctypes.cast(ptrs, ctypes.c_void_p),
-                                                     _lib.ptr(coef), _lib.ptr(zsum), _lib.ptr(zsq), stream))
-    finally:
-        lib.bluest_group_sums_slab(before.value, None)                 # the budget is process-wide: leave it as it was
+    with _lib.staging_budget(slab_bytes):
+        _lib.check(_lib.lib().bluest_field_weighted_moments(S, d, _lib.ptr(counts), _lib.ptr(sizes), ctypes.cast(ptrs, ctypes.c_void_p),
+                                                            _lib.ptr(coef), _lib.ptr(zsum), _lib.ptr(zsq), stream))
     return [(int(N), zsum[s].copy(), zsq[s].copy()) for s, N in enumerate(counts.tolist())]
 
 

@@ -127,15 +127,10 @@ def field_group_sums(values, weights=None, repeat_of=None, R=None, slab_bytes=SL
             raise ValueError("repeat_of must have one entry per segment")
         R = int(repeat_of[-1]) + 1 if R is None else int(R)
         mu = np.empty((max(R, 0), d))
-    lib = _lib.lib()
-    before = ctypes.c_int64(0)
-    _lib.check(lib.bluest_group_sums_slab(max(int(slab_bytes), 1), ctypes.byref(before)))
-    try:
-        _lib.check(lib.bluest_field_sums(S, d, _lib.ptr(counts), _lib.ptr(sizes), ctypes.cast(ptrs, ctypes.c_void_p),
-                                         _lib.ptr(weights), int(R or 0), _lib.ptr(repeat_of) if weights is not None else None,
-                                         _lib.ptr(sums), _lib.ptr(mu), stream))
-    finally:
-        lib.bluest_group_sums_slab(before.value, None)                 # the budget is process-wide: leave it as it was
+    with _lib.staging_budget(slab_bytes):
+        _lib.check(_lib.lib().bluest_field_sums(S, d, _lib.ptr(counts), _lib.ptr(sizes), ctypes.cast(ptrs, ctypes.c_void_p),
+                                                _lib.ptr(weights), int(R or 0), _lib.ptr(repeat_of) if weights is not None else None,
+                                                _lib.ptr(sums), _lib.ptr(mu), stream))
     ends = np.cumsum(sizes)
     out = [sums[e - l:e].copy() for e, l in zip(ends.tolist(), sizes.tolist())]
     return out if weights is None else (out, mu)

@@ -53,14 +53,9 @@ def group_moments(values, slab_bytes=SLAB_BYTES):
     T = int(sizes.sum())
     tri = (sizes.astype(np.int64) * (sizes.astype(np.int64) + 1)) // 2
     first, second = np.empty((n_out, T)), np.empty((n_out, int(tri.sum())))
-    lib = _lib.lib()
-    before = ctypes.c_int64(0)
-    _lib.check(lib.bluest_group_sums_slab(max(int(slab_bytes), 1), ctypes.byref(before)))
-    try:
-        _lib.check(lib.bluest_group_moments(len(keep), n_out, _lib.ptr(counts), _lib.ptr(sizes), ctypes.cast(ptrs, ctypes.c_void_p),
-                                            _lib.ptr(first), _lib.ptr(second), stream))
-    finally:
-        lib.bluest_group_sums_slab(before.value, None)                 # the budget is process-wide: leave it as it was
+    with _lib.staging_budget(slab_bytes):
+        _lib.check(_lib.lib().bluest_group_moments(len(keep), n_out, _lib.ptr(counts), _lib.ptr(sizes),
+                                                   ctypes.cast(ptrs, ctypes.c_void_p), _lib.ptr(first), _lib.ptr(second), stream))
     return _unpacked(counts, sizes, first, second)
 
 
