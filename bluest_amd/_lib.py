@@ -103,6 +103,7 @@ SIGNATURES = {
     "bluest_group_moments": [c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "bluest_pilot_moments4": [c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "bluest_field_weighted_moments": [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "bluest_field_group_moments": [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
 
 

@@ -716,6 +716,59 @@ int bluest_pilot_moments4(int64_t N, int L, int n_out, const double *values, con
 int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t *counts, const int32_t *sizes, const double *const *values,
                                   const double *coef, double *zsum, double *zsq, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Part 16 -- second moments of a field's models in the inner product <a, b> = sum_c w_c a_c b_c, over many ragged segments in
+ * one call: Part 13 for a field, what the unbiased covariance of every drawn model group of a field output is made of (the
+ * reference has no counterpart).  Segments, counts, sizes, values[s] (counts[s] x sizes[s] x d row-major float64, a host OR a
+ * device pointer per segment, 8-byte aligned, null allowed where counts[s] == 0) and the staging budget
+ * (bluest_group_sums_slab) are exactly those of bluest_field_sums and Part 15.  w: host, d weights, finite and >= 0, as in Part
+ * 12.  Host outputs, float64.
+ * THE SHIFT.  Every value enters as d_ij[c] = values[s][i][j][c] - values[s][0][j][c], the segment's first sample subtracted: one
+ * rounding, as in Parts 13 and 15.
+ *   second (P = sum of sizes[s] (sizes[s] + 1) / 2, packed per segment as in Part 13):  pair j <= k:  sum_i sum_c w_c d_ij[c] d_ik[c]
+ *   cross  (P, the same packing):                      pair j <= k:  sum_c w_c f_j[c] f_k[c]  with  f_j[c] = sum_i d_ij[c]
+ *   first  (T x d, T = sum of sizes; MAY BE NULL):     first[c0(s) + j][c] = f_j[c], c0(s) as in Part 11.  With first null,
+ *          second and cross keep their bits: f is formed on the device either way, and only its copy to the host is left out.
+ * The unbiased covariance of segment s in the inner product is (second - cross / N) / (N - 1), N = counts[s]: the shift drops
+ * out.  cross is formed on the device because the copy of T d per-component sums to the host is most of a field_sums call;
+ * here L (L + 1) doubles per segment travel, and T d only where the caller asks for first.
+ * THE ORDER OF EVERY OPERATION IS FIXED.
+ *   f:      per (segment, column, component) steps 1-3 of Part 11 applied to d.
+ *   second: per pair j <= k.  The samples are cut into chunks of BLUEST_GSUM_CHUNK, the components into tiles of
+ *           BLUEST_FIELD_TILE = 8 (the last may be shorter).  Per (chunk, tile) and class k = 0..7 of sixteen samples, q_k starts
+ *           from +0.0 and takes q = fma(w_c * a, b, q) with a = d_ij[c], b = d_ik[c] and w_c * a rounded to float64, over the
+ *           class's samples in ascending order and inside a sample over the tile's components in ascending order.  The classes
+ *           join as ((q_0 + q_1) + (q_2 + q_3)) + ((q_4 + q_5) + (q_6 + q_7)) (a class without samples is +0.0).  Per chunk the
+ *           tiles join as in Part 12: lane l = 0..63 adds the tiles l, l + 64, ... in ascending order from +0.0, then for off =
+ *           32, 16, 8, 4, 2, 1 lane l < off takes p_l = p_l + p_(l + off); the chunk's value is p_0.  The chunks fold as in step
+ *           3 of Part 11.
+ *   cross:  per pair j <= k and tile, x = fma(w_c * f_j[c], f_k[c], x) over the tile's components in ascending order from +0.0
+ *           (w_c * f_j[c] rounded to float64); the tiles join by the same lane sums and tree.
+ * ANCHORS.
+ *   - With d == 1 and w == {1.0}, second and first are bit for bit those of bluest_group_moments (n_out = 1) on the same
+ *     values: there is one tile of one component, 1.0 * a is a, so q_k is Part 13's class sum; the tile join adds it to +0.0
+ *     (a sum that starts from +0.0 is never -0.0) and the other lanes hold +0.0, so the chunk's value is the class tree's.
+ *   - With sizes[s] == 1 and w one-hot at component c, second[s] is bit for bit zsq[s][c] of Part 15 with coefficient 1.0:
+ *     there z = fma(1.0, d, +0.0) = d (and -0.0 squares like +0.0), here the terms fma(+0.0 * a, b, q) of the other components
+ *     leave q alone for finite values, the other tiles give +0.0, and the joins add +0.0.  For such a segment f is bit for bit
+ *     zsum of Part 15 with coefficient 1.0, and at d == 1 it is bit for bit first of Part 13, for the same reason.
+ *   - For identical j and k, cross is sum_c w_c f_j[c]^2 in the order above.
+ * So the results of segment s are a function of that segment's values, of w, of BLUEST_GSUM_CHUNK and of BLUEST_FIELD_TILE only:
+ * not of the device, of the other segments of the call, of the segment's position, of host or device memory, of the alignment of
+ * its base, of where a slab ends (the first samples of the host segments travel apart from the slabs), or of the launch shape
+ * (how many tiles a workgroup takes side by side and how many samples it stages in LDS at a time follow sizes[s] and d).  No
+ * atomics, nothing sized by the number of compute units, no matrix instructions.  counts[s] == 0 and counts[s] == 1 give +0.0
+ * everywhere.  NaN / Inf propagate (Inf - Inf is NaN).
+ * BLUEST_ERR_ARG, returned before anything is written: the cases of bluest_field_sums (S < 1, d < 1, a null counts / sizes /
+ * values, a size outside 1..BLUEST_MAX_MODELS, a negative count, a null or misaligned values[s] with counts[s] > 0, more than
+ * 2^31 - 1 columns, chunks or column-components T d), a null w, second or cross, a weight that is not finite or is negative,
+ * more than 2^31 - 1 packed pairs P, partial sums ((pair, chunk, tile) or (chunk, column, component)) or (chunk, block of
+ * tiles) workgroups.  Without a device BLUEST_ERR_NOGPU: there is no CPU path.  Synchronous on `stream`; allocates one arena of
+ * device memory and frees it.
+ * --------------------------------------------------------------------------------------------------------- */
+int bluest_field_group_moments(int64_t S, int64_t d, const int64_t *counts, const int32_t *sizes, const double *const *values,
+                               const double *w, double *second, double *cross, double *first, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
