@@ -104,6 +104,8 @@ SIGNATURES = {
     "bluest_pilot_moments4": [c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "bluest_field_weighted_moments": [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "bluest_field_group_moments": [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "bluest_field_pilot_moments": [c_i64, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "bluest_field_pilot_scratch": [c_i64, c_i64p],
 }
 
 

@@ -244,14 +244,25 @@ class FieldOutputsMixin(object):
         return [_joined([share[n] for share in parts]) for n in range(self.n_outputs)]
 
     # ---- pilot samples (bluest_amd.pilot.PilotMixin) ----------------------------------------------------------------------------------
+    def _field_pilot_count(self, ls, N):
+        """how many of the N joint pilot samples of the models `ls` are drawn now: all of them.
+        bluest_amd.field_pilot_errors.FieldPilotErrorsMixin draws what its earlier rounds have not"""
+        return N
+
+    def _field_pilot_gathered(self, ls, values):
+        """rank 0: per output the values just drawn, all ranks' shares joined [count, L, d_n]; returns the values to sum, per
+        output [N, L, d_n].  Nothing to do here; FieldPilotErrorsMixin puts the values of its earlier rounds in front"""
+        return values
+
     def _pilot_sums(self, ls, N):
         """blue_fn's nested results -- sumse[n][i], sumsc[n] [L, L], sumsd1[n][i][j], sumsd2[n][i][j] (i < j, else 0) -- from ONE
         field_statistics call per output over all the values"""
         self._check_field_width(len(ls))
         ws, is_field = self._field_weights()
-        values = self._gathered(draw_field_values(self, ls, N, [len(w) for w in ws], device_ok=True))
+        values = self._gathered(draw_field_values(self, ls, self._field_pilot_count(ls, N), [len(w) for w in ws], device_ok=True))
         sums = None
         if values is not None:
+            values = self._field_pilot_gathered(ls, values)
             L = len(ls)
             sumse, sumsc, sumsd1, sumsd2 = [], [], [], []
             for n in range(self.n_outputs):

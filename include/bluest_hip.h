@@ -769,6 +769,51 @@ int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t *counts, c
 int bluest_field_group_moments(int64_t S, int64_t d, const int64_t *counts, const int32_t *sizes, const double *const *values,
                                const double *w, double *second, double *cross, double *first, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Part 17 -- what the standard errors of Part 12's pilot estimates are made of: per pair of models the sums, over the pilot
+ * samples, of the PER-SAMPLE centred inner product and of its square (the reference has no counterpart).  One output per call.
+ * values "hd" (host or device, detected as in Part 10; 8-byte aligned): N x L x d row-major float64 as in Part 12.  w: host, d
+ * weights, finite and >= 0.  centre: host, L x d: the point the samples are centred at, for the standard errors the
+ * per-component mean sumse / N of Part 12.  Host outputs, float64, L x L each:
+ *   q_s(i, j) = sum_c w_c a b,   a = y_i[c] - centre_i[c], b = y_j[c] - centre_j[c]           (sample s, pair i <= j)
+ *   r_s(i, j) = sum_c w_c t t,   t = (y_i[c] - y_j[c]) - (centre_i[c] - centre_j[c])           (from the explicit differences, i < j)
+ *   qfirst = q_0,   qs1 = sum_s (q_s - q_0),   qs2 = sum_s (q_s - q_0)^2      full and symmetric: a pair i <= j is computed once
+ *                                                                              and mirrored (fma(w a, b, .) is not symmetric)
+ *   rfirst = r_0,   rs1 = sum_s (r_s - r_0),   rs2 = sum_s (r_s - r_0)^2      at i < j, every other entry 0
+ * rfirst, rs1 and rs2 may ALL be null: no difference sums (the q outputs keep their bits).  The shift by the first sample keeps
+ * the digits of qs2 - qs1^2 / N when the mean of q_s is far above its spread.  The standard error of the mean of q_s is
+ * sqrt(max(qs2 - qs1^2 / N, 0) / (N (N - 1))): the first-order (delta-method) error of the covariance estimate mean_s q_s.
+ * THE ORDER OF EVERY OPERATION IS FIXED.  The components are cut into strips of BLUEST_FIELD_STRIP = 512 consecutive components,
+ * the samples into chunks of BLUEST_PILOT_CHUNK consecutive samples (the last of either may be shorter).
+ *   per (sample, pair, strip), over the strip's components c in ascending order from +0.0:
+ *       p = fma(w_c * a, b, p);   p' = fma(w_c * t, t, p')      (a, b, t as above, each difference and w_c * a, w_c * t rounded
+ *                                                                 to float64; a thread walks the whole chain, nothing is joined)
+ *   per (sample, pair): q_s = the strips' values added in ascending order from +0.0; r_s likewise.
+ *   per (pair, chunk), over the chunk's samples in ascending order from +0.0:  u = q_s - q_0;  s1 = s1 + u;  s2 = fma(u, u, s2)
+ *   per pair: the chunks' s1 and s2 added in ascending order from +0.0.
+ * So the result is a function of `values`, `w`, `centre`, BLUEST_FIELD_STRIP and BLUEST_PILOT_CHUNK only: the same bits from host
+ * or device memory, at any 8-byte alignment of the base, under any staging budget (bluest_group_sums_slab) and any scratch limit,
+ * and whatever shape the launch takes -- how many samples a workgroup stages in LDS and how wide its column blocks are follow L
+ * and d.  No atomics, nothing sized by the number of compute units.  With w one-hot at component c the results are those of the
+ * d = 1 call on that component (fma(+0.0 * a, b, p) leaves p alone for finite values).  NaN / Inf propagate: a NaN in model i
+ * reaches the pairs of model i and no other.  N == 1 gives +0.0 in the four sums.
+ * The per-sample values pass through device scratch, (d / BLUEST_FIELD_STRIP rounded up, + 1 where that is above 1) x L (L + 1)
+ * doubles per sample with the r outputs, half of it without.  The samples are processed in runs of whole chunks so that the
+ * scratch stays under bluest_field_pilot_scratch's limit (at least one chunk) and, for host input, the staged values under the
+ * budget of bluest_group_sums_slab; every run is read once.
+ * bluest_field_pilot_scratch(bytes, previous): that limit for the calls that follow (process-wide; default
+ * BLUEST_FIELD_PILOT_SCRATCH_BYTES); bytes == 0 only reads it; `previous` may be null.
+ * BLUEST_ERR_ARG, returned before anything is launched: the cases of bluest_field_stats (L outside 1..BLUEST_MAX_MODELS, d < 1,
+ * N < 1, a null values / w, a weight that is not finite or is negative), a null centre, qfirst, qs1 or qs2, some but not all of
+ * rfirst / rs1 / rs2 null, values not 8-byte aligned, more than 2^31 - 1 values L d per sample or chunks.  Without a device
+ * BLUEST_ERR_NOGPU.  Synchronous on `stream`; allocates one arena of device memory and frees it.
+ * --------------------------------------------------------------------------------------------------------- */
+#define BLUEST_FIELD_STRIP         512
+#define BLUEST_FIELD_PILOT_SCRATCH_BYTES (256LL << 20)
+int bluest_field_pilot_moments(int64_t N, int L, int64_t d, const double *values, const double *w, const double *centre,
+                               double *qfirst, double *qs1, double *qs2, double *rfirst, double *rs1, double *rs2, void *stream);
+int bluest_field_pilot_scratch(int64_t bytes, int64_t *previous);
+
 #ifdef __cplusplus
 }
 #endif
