@@ -106,6 +106,10 @@ SIGNATURES = {
     "bluest_field_group_moments": [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "bluest_field_pilot_moments": [c_i64, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "bluest_field_pilot_scratch": [c_i64, c_i64p],
+    "bluest_field_op_create": [c_i64, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)],
+    "bluest_field_op_shape": [c_vp, c_i64p, c_i64p, c_i64p],
+    "bluest_field_op_destroy": [c_vp],
+    "bluest_field_map": [c_i64, c_int, c_i64, c_vp, c_vp, c_vp, c_vp],
 }
 
 

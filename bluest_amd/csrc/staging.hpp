@@ -1,5 +1,5 @@
 // staging.hpp -- what the sample-sum entry points (pilot.hip, pilot4.hip, gsums.hip, fields.hip, moments.hip, field_moments.hip,
-// field_cov.hip, field_pilot.hip) share: telling a host pointer from a device pointer, the one device allocation of a call, the pair -> thread map of the pilot
+// field_cov.hip, field_pilot.hip, field_map.hip) share: telling a host pointer from a device pointer, the one device allocation of a call, the pair -> thread map of the pilot
 // statistics, and the mechanism of the four calls over many ragged segments (bluest_group_sums, bluest_field_sums,
 // bluest_group_moments, bluest_field_weighted_moments):
 //   - the checks of a segment's arguments (check_segment);

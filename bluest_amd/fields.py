@@ -140,21 +140,27 @@ def draw_field_values(problem, ls, N, widths, device_ok=False):
     """this rank's share of N joint samples of the models `ls`, per output an array [share, len(ls), widths[n]]: the field-aware
     sibling of bluest_amd._blue_fn.draw_values, with the same sequence of sampler / evaluate calls (bluest/blue_fn.py:106-129).
     Ps[n][i] holds widths[n] components per sample: shape [d] for a batch of one, else [N2, d] (a number: N2 values).  With
-    `device_ok`, an evaluate that returns CUDA tensors keeps its batches on the device."""
+    `device_ok`, an evaluate that returns CUDA tensors keeps its batches on the device.
+    A problem may have a method _field_batch_hook(ls) (bluest_amd.field_maps.MappedFieldsMixin): it returns per output None, or
+    (the widths of the models `ls` themselves, a function from their len(ls) raw batches [N2, d_i] to [N2, len(ls), widths[n]]).
+    Such an output is checked for width and finiteness as it arrives and mapped, batch by batch, before it is kept."""
     comm = problem.get_comm()
     size, rank = comm.Get_size(), comm.Get_rank()
     mine = int(N) // size + (1 if rank < int(N) % size else 0)
     batched = len(signature(problem.sampler).parameters) > 1
     N1 = int(problem.params["sample_batch_size"]) if batched else 1
     n_out, L = problem.n_outputs, len(ls)
+    hook = getattr(problem, "_field_batch_hook", None)
+    raw = hook(ls) if hook is not None else [None] * n_out
 
     def shaped(v, n, i, N2):
-        d = widths[n]
+        d = widths[n] if raw[n] is None else raw[n][0][i]
         count = v.numel() if hasattr(v, "numel") else v.size
         last = v.shape[-1] if len(v.shape) > 0 else 1
         if count != N2 * d or (d > 1 and last != d):
-            raise BLUESTError("output %d of model %d has shape %s for a batch of %d samples: output_weights() declares %d "
-                              "component(s)" % (n, ls[i], tuple(v.shape), N2, d))
+            raise BLUESTError("output %d of model %d has shape %s for a batch of %d samples: %s declares %d "
+                              "component(s)" % (n, ls[i], tuple(v.shape), N2, "output_weights()" if raw[n] is None else
+                                                "output_operators()", d))
         return v.reshape(N2, d)
 
     out, batches, done = None, [], 0
@@ -165,8 +171,11 @@ def draw_field_values(problem, ls, N, widths, device_ok=False):
             Ps = problem.evaluate(ls, samples)
             if device_ok and _on_gpu(Ps[0][0]):
                 import torch
-                Ps = [torch.stack([shaped(Ps[n][i], n, i, N2) for i in range(L)], dim=1).to(torch.float64) for n in range(n_out)]
-                finite = all(bool(torch.isfinite(t).all()) for t in Ps)
+                Ps = [torch.stack([shaped(Ps[n][i], n, i, N2) for i in range(L)], dim=1).to(torch.float64) if raw[n] is None else
+                      [shaped(Ps[n][i], n, i, N2).to(torch.float64) for i in range(L)] for n in range(n_out)]
+                finite = all(bool(torch.isfinite(t).all()) for P in Ps for t in (P if isinstance(P, list) else [P]))
+                if finite:
+                    Ps = [raw[n][1](P) if isinstance(P, list) else P for n, P in enumerate(Ps)]
             else:
                 finite = _all_finite(Ps)
             if finite:
@@ -179,6 +188,9 @@ def draw_field_values(problem, ls, N, widths, device_ok=False):
             if out is None:
                 out = [np.empty((mine, L, widths[n])) for n in range(n_out)]
             for n in range(n_out):
+                if raw[n] is not None:
+                    out[n][done:done + N2] = raw[n][1]([shaped(np.asarray(Ps[n][i], dtype=np.float64), n, i, N2) for i in range(L)])
+                    continue
                 for i in range(L):
                     out[n][done:done + N2, i, :] = shaped(np.asarray(Ps[n][i], dtype=np.float64), n, i, N2)
         done += N2

@@ -814,6 +814,55 @@ int bluest_field_pilot_moments(int64_t N, int L, int64_t d, const double *values
                                double *qfirst, double *qs1, double *qs2, double *rfirst, double *rs1, double *rs2, void *stream);
 int bluest_field_pilot_scratch(int64_t bytes, int64_t *previous);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Part 18 -- fields on per-model meshes: sparse maps B_l (q x d_l) that take the d_l components of model l into a space of q
+ * components all models of an output share -- point evaluation, prolongation to the finest mesh, restriction to an observation
+ * grid, evaluation at quadrature points.  After the map, Parts 12 and 15 to 17 apply as they are to the array [N, L, q].  (The
+ * reference has no counterpart: its field example reduces every solution to two point values on the host.)
+ * AN OPERATOR is given once as a host CSR matrix -- indptr (q + 1), indices and data (nnz = indptr[q] each) -- and is checked,
+ * re-laid out for the device and uploaded by bluest_field_op_create; the handle owns its device memory until
+ * bluest_field_op_destroy, and the caller's arrays are not kept.  bluest_field_op_shape reads q, d and nnz back (each pointer
+ * may be null).  BLUEST_ERR_ARG from create, before anything is allocated: q < 1 or d < 1, q, d or nnz above 2^31 - 1, a null
+ * indptr / op (or indices / data with nnz > 0), indptr[0] != 0, indptr decreasing, an index outside 0..d-1, a coefficient that
+ * is not finite.  Without a device BLUEST_ERR_NOGPU.
+ * THE CALL.  ops: L handles, or null = all identity; a null ENTRY is the identity and needs d_l == q.  values: L pointers,
+ * values[l] N x d_l row-major float64, each a host OR a device pointer (detected as in Part 10), 8-byte aligned.  out: N x L x q
+ * row-major float64, host or device, 8-byte aligned.
+ *   out[s][l][r] = row r of ops[l] applied to sample s of values[l].
+ * THE ORDER OF EVERY OPERATION IS FIXED.  The entries k = indptr[r] .. indptr[r + 1] - 1 of a row are taken in their STORED
+ * order: they are neither sorted nor merged, and a column may occur twice.  They are cut into strips of BLUEST_FIELD_MAP_STRIP =
+ * 512 consecutive entries (the last may be shorter).
+ *   per strip, from +0.0, in ascending k:   p = fma(data[k], y[s][indices[k]], p)
+ *   per row: the strips' values added in ascending order from +0.0.
+ * A row of at most one strip is that one chain (a chain that starts from +0.0 never ends in -0.0, so adding it to +0.0 changes
+ * no bit): every finite-element prolongation.  An empty row gives +0.0.  An identity entry copies the value's 64 bits, -0.0 and
+ * the payload of a NaN included.
+ * So the result is a function of the operator, of the values and of BLUEST_FIELD_MAP_STRIP only: the same bits from host or
+ * device memory (the inputs mixed freely, the output on either side), at any 8-byte alignment, under any staging budget
+ * (bluest_group_sums_slab), for a model alone or among 64, and whatever shape the launch takes -- rows of at most one strip run
+ * with a lane per row over a sliced-ELL copy of the operator, longer rows with a lane per sample that walks the strips in order;
+ * which of the two a row gets follows from its length only.  No atomics, nothing sized by the number of compute units, no
+ * matrix instructions.
+ * NaN / Inf propagate: a NaN at y[s][c] reaches exactly the rows that name column c, on that sample and in that model, whatever
+ * their coefficient (0 * NaN is NaN; a row padded for the device layout never executes its padding).  A coefficient 0 on a
+ * finite value leaves the chain as it is.
+ * Host values and a host `out` pass through one arena of device memory in runs of whole samples under the budget of
+ * bluest_group_sums_slab (at least one sample per run); an output element depends on one sample only, so a run's end never
+ * shows.  Device values are read where they lie, a device `out` is written where it lies.
+ * BLUEST_ERR_ARG, returned before anything is launched or allocated: L outside 1..BLUEST_MAX_MODELS, N < 0, q < 1, a null values,
+ * a null values[l] or out with N > 0, an entry of ops that is not a live handle or whose q differs from the call's, values[l]
+ * or out not 8-byte aligned.  N == 0 returns BLUEST_OK and writes nothing.  Without a device BLUEST_ERR_NOGPU: there is no CPU
+ * path.  Synchronous on `stream`.
+ * --------------------------------------------------------------------------------------------------------- */
+typedef struct bluest_field_op *bluest_field_op_t;
+#define BLUEST_FIELD_MAP_STRIP     512
+int bluest_field_op_create(int64_t q, int64_t d, const int64_t *indptr, const int32_t *indices, const double *data,
+                           bluest_field_op_t *op);
+int bluest_field_op_shape(bluest_field_op_t op, int64_t *q, int64_t *d, int64_t *nnz);
+int bluest_field_op_destroy(bluest_field_op_t op);
+int bluest_field_map(int64_t N, int L, int64_t q, const bluest_field_op_t *ops, const double *const *values, double *out,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif
