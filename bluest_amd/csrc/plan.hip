@@ -57,13 +57,11 @@ template <> __device__ __forceinline__ int4 load_cols4<uint16_t>(const uint16_t 
 // Phi pass: one wavefront per chunk of CH = 256*iters entries; lane l owns entries [4l, 4l+4) of each 256-block.
 // Prologue of both chunk kernels: what the stream needs arrives in scalar registers with the wavefront (see "Arguments" below), the
 // gate of a launch that has one costs two scalar round trips (pointer, word), and the slot of the chunk's partial -- needed behind
-// the loop only -- is a scalar load without a branch (a plan without a slot table reads a dummy word and keeps the chunk
-// number), so no wait stands between the launch and the first streaming load.
+// the loop only -- is a scalar load issued behind the stream's first loads by a plan that has a slot table (another keeps the
+// chunk number), so no wait stands between the launch and the first streaming load.
 // Tail: every workgroup is whole wavefronts and the early exits are wave-uniform, so all 64 lanes reach the reductions, which
 // run on the VALU (wave_sum_dpp / wave_max_dpp, common.hpp).
-// The slot word of a plan without a slot table is a dummy read of the first four bytes of the column stream (always there: the
-// plan has at least one chunk); its value is discarded, only the absence of a branch around the load matters.
-// What the compiler makes of this prologue and of the addressing below is recorded in profiles/r09_isa_counts.txt (tools/isa_counts.py):
+// What the compiler makes of this prologue and of the addressing below is recorded in profiles/r10_isa_counts.txt (tools/isa_counts.py):
 // re-check it there after a toolchain update.
 // Addressing of both chunk kernels: a wavefront's chunk, its output block and every base of vals / cols / m / partial are
 // wave-uniform and live on the SALU; a lane adds one 32-bit byte offset per stream (the loads and the store take the scalar base
@@ -79,58 +77,99 @@ template <int WPB> __device__ __forceinline__ uint32_t phi_wave_chunk()
 }
 // Arguments of both chunk kernels.  The first 14 dwords of a kernel's argument list arrive in scalar registers with the wavefront
 // (kernarg preload, the -mllvm option bluest_amd/build.py gives this unit), so everything the common path needs in front of its first
-// streaming load stands there, as plain pointers and 32-bit scalars: vals, cols, m, pslot, iters, the chunk count, n_out, n_cand
-// and a flags word (PHI_HAS_GATE: the gate pointer is loaded, one scalar round trip, only by a launch that has one).  The others
-// are first needed by the store: their scalar loads are issued in front of the stream and waited for behind the issue of its first
-// loads (phi_late_args, called in the loop), so the round trip to the argument segment runs under the one to the stream.
-constexpr uint32_t PHI_HAS_GATE = 1u;
+// streaming load stands there in the form the loads take it, computed once at the launch site: vals, cols, m, pslot, CH = 256 * iters
+// (entries of a chunk), the chunk count, one output's values in bytes (per_out_bytes = chunks per output * CH * 8, the step from
+// one output's base to the next), n_out with the flags in its top bits (PHI_HAS_GATE: the gate pointer is loaded, one scalar round
+// trip, only by a launch that has one) and n_cand.  The others are first needed by the store: they are waited for behind the issue
+// of the stream's first loads (phi_late_args), so the round trip to the argument segment runs under the one to the stream.
+// Entry: both kernels open with one sweep over a 256-block written out on its own (sweep(std::true_type)).  From the preload entry to
+// the issue of the column load and the first output's two value loads a wavefront forms its chunk, one 64-bit base per stream and the
+// lane's two 32-bit offsets, nothing else.  The bases of the second and later outputs follow behind an ordering point
+// (phi_issue_point), and everything only the stores need -- the slot word, the owner and index of wave_sum_multi, the stride between
+// outputs' partials, the loop count -- behind the loads of the first (at most four) outputs and another such point: it runs under a
+// round trip that has to be waited for anyway.  All of it is loop-invariant: the loops over the chunk's further 256-blocks and over
+// the candidates stand behind the opening sweep and reuse it.  profiles/r10_isa_counts.txt has the listing.
+constexpr uint32_t PHI_HAS_GATE = 1u << 31, PHI_N_OUT_MASK = ~PHI_HAS_GATE;
 template <class... A> __device__ __forceinline__ void phi_late_args(const A &...a) { kernarg_now(a...); }
+// nothing moves across this point, neither in the compiler's passes nor in its instruction scheduler
+__device__ __forceinline__ void phi_issue_point()
+{
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+// the partials are stored through a pointer the compiler knows to be global memory: behind uniform_value_here it has lost that, and
+// with a flat store in the loop every vector wait in it was a wait for ALL loads (the columns' wait took the value stream with it)
+typedef double PhiPair __attribute__((ext_vector_type(2)));      // (a plain vector type: double2 is a class for the host compiler)
+__device__ __forceinline__ void store_partial(char *p, double s, double amax)
+{
+    PhiPair w;
+    w.x = s; w.y = amax;
+    *(__attribute__((address_space(1))) PhiPair *)p = w;
+}
+// the value stream's bases likewise: they are formed in steps, output by output, and are global memory by their type
+using PhiStream = const __attribute__((address_space(1))) char *;
+__device__ __forceinline__ double2 stream_pair(PhiStream p)
+{
+    const PhiPair w = *reinterpret_cast<const __attribute__((address_space(1))) PhiPair *>(p);
+    return make_double2(w.x, w.y);
+}
 template <int WPB, typename COLT>
 __global__ __launch_bounds__(64 * WPB) void k_phi_chunks(const double *__restrict__ vals, const COLT *__restrict__ cols,
                                                     const double *__restrict__ m, const int32_t *__restrict__ pslot,
-                                                    int iters, uint32_t n_chunks, int n_out, int n_cand, uint32_t flags,
+                                                    uint32_t CH, uint32_t n_chunks, uint64_t per_out_bytes, uint32_t n_out_flags, int n_cand,
                                                     const int32_t *__restrict__ gate, int64_t m_stride, int64_t pstride,
                                                     int slots_per_output, double2 *__restrict__ partial)
 {
-    (void)n_out; (void)slots_per_output;      // (one argument list for both chunk kernels)
+    (void)per_out_bytes; (void)slots_per_output;      // (one argument list for both chunk kernels)
     const uint32_t chunk = phi_wave_chunk<WPB>();
     const uint32_t lane = threadIdx.x & 63;
-    if (flags & PHI_HAS_GATE) { if (uniform_word(gate) == 0) return; }      // device-side predication (SPG line-search slots)
+    if (__builtin_expect((n_out_flags & PHI_HAS_GATE) != 0, 0)) { if (uniform_word(gate) == 0) return; }      // device-side predication (SPG line-search slots)
     if (chunk >= n_chunks) return;
-    // where the fold expects this chunk's partial (in flight until the store; both early exits are scalar branches without a
-    // wait of their own, so the load loses nothing behind them)
-    const int32_t slot_ld = uniform_word(pslot ? pslot + chunk : reinterpret_cast<const int32_t *>(cols));
-    const uint64_t base = (uint64_t)chunk * ((uint32_t)iters * 256u);      // entries in front of this chunk
-    const char *vb = reinterpret_cast<const char *>(vals + base);
+    const uint64_t base = (uint64_t)chunk * CH;      // entries in front of this chunk
+    const PhiStream vb = (PhiStream)(vals + base);
     const char *cb = reinterpret_cast<const char *>(cols + base);
     const double *mc = m;
+    double s = 0.0, amax = 0.0;
+    uint32_t vo = lane * 32u, co = lane * (uint32_t)(4 * sizeof(COLT));
+    uint32_t iters = 1;
+    int32_t slot_ld = 0;
+    // one 256-block of the chunk; first: the sweep that opens the kernel, with what only the store needs behind its loads
+    auto sweep = [&](auto first) {
+        const int4 cc = load_cols4<COLT>(reinterpret_cast<const COLT *>(cb + co));
+        const double2 v01 = stream_pair(vb + vo), v23 = stream_pair(vb + vo + 16);
+        if constexpr (decltype(first)::value) {
+            phi_issue_point();
+            iters = uniform_value_here(CH) >> 8;
+            phi_late_args(m_stride, pstride, partial);      // (one scalar wait, behind the issue of the stream's loads)
+            // where the fold expects this chunk's partial: a scalar load behind that wait, in flight until the store (a plan
+            // without a slot table keeps the chunk number)
+            if (pslot) slot_ld = uniform_word(pslot + uniform_value_here(chunk));
+        }
+        const double m0 = mc[cc.x], m1 = mc[cc.y], m2 = mc[cc.z], m3 = mc[cc.w];
+        s = fma(v01.x, m0, s);
+        s = fma(v01.y, m1, s);
+        s = fma(v23.x, m2, s);
+        s = fma(v23.y, m3, s);
+        amax = fmax(fmax(amax, fmax(fabs(m0), fabs(m1))), fmax(fabs(m2), fabs(m3)));
+        vo += 2048u; co += (uint32_t)(256 * sizeof(COLT));
+    };
+    sweep(std::true_type());
     int64_t pdone = 0;      // candidates' partials in front of this one, in bytes
-    for (int c = 0; c < n_cand; c++) {
-        double s = 0.0, amax = 0.0;
-        uint32_t vo = lane * 32u, co = lane * (uint32_t)(4 * sizeof(COLT));
-        int it = 0;
-        do {      // (a chunk has at least one 256-block)
-            const double2 *vp = reinterpret_cast<const double2 *>(vb + vo);
-            const double2 v01 = vp[0], v23 = vp[1];
-            const int4 cc = load_cols4<COLT>(reinterpret_cast<const COLT *>(cb + co));
-            phi_late_args(m_stride, pstride, partial);      // (one scalar wait: it takes the slot word with it, see below)
-            const double m0 = mc[cc.x], m1 = mc[cc.y], m2 = mc[cc.z], m3 = mc[cc.w];
-            s = fma(v01.x, m0, s);
-            s = fma(v01.y, m1, s);
-            s = fma(v23.x, m2, s);
-            s = fma(v23.y, m3, s);
-            amax = fmax(fmax(amax, fmax(fabs(m0), fabs(m1))), fmax(fabs(m2), fabs(m3)));
-            vo += 2048u; co += (uint32_t)(256 * sizeof(COLT));
-        } while (++it < iters);
+    uint32_t it = 1;
+    for (int c = 0;;) {
+        for (; it < iters; it++) sweep(std::false_type());
         s = wave_sum_dpp(s);
         amax = wave_max_dpp(amax);
-        // (the slot word is a scalar load like the late arguments, so the wait for those, in the loop behind the issue of the
-        //  first stream loads, has brought it in too: no wait of its own is left here)
         const uint32_t slot = pslot ? (uint32_t)uniform_value_here(slot_ld) : chunk;
         char *pc = reinterpret_cast<char *>(uniform_value_here(partial)) + pdone;
-        if (lane == 0) *reinterpret_cast<double2 *>(pc + slot * 16u) = make_double2(s, amax);
+        if (lane == 0) store_partial(pc + slot * 16u, s, amax);
+        if (++c >= n_cand) break;
         mc += uniform_value_here(m_stride);      // (not hoisted in front of the loop, where they would be waited for)
         pdone += uniform_value_here(pstride) * (int64_t)sizeof(double2);
+        // (the next candidate's offsets taken as they are here: a chunk of one 256-block has the same columns for every candidate,
+        //  and their load is not to be moved in front of the loops)
+        s = 0.0; amax = 0.0; it = 0;
+        vo = lane_value_here(lane * 32u); co = lane_value_here(lane * (uint32_t)(4 * sizeof(COLT)));
     }
 }
 
@@ -143,81 +182,102 @@ __global__ __launch_bounds__(64 * WPB) void k_phi_chunks(const double *__restric
 template <int OB, int WPB, typename COLT>
 __global__ __launch_bounds__(64 * WPB) void k_phi_chunks_shared(const double *__restrict__ vals, const COLT *__restrict__ cols,
                                                            const double *__restrict__ m, const int32_t *__restrict__ pslot,
-                                                           int iters, uint32_t ncpo, int n_out, int n_cand, uint32_t flags,
+                                                           uint32_t CH, uint32_t ncpo, uint64_t per_out_bytes, uint32_t n_out_flags, int n_cand,
                                                            const int32_t *__restrict__ gate, int64_t m_stride, int64_t pstride,
                                                            int slots_per_output, double2 *__restrict__ partial)
 {
     const uint32_t chunk = phi_wave_chunk<WPB>();
     const uint32_t lane = threadIdx.x & 63;
-    const uint32_t o0 = blockIdx.y * OB;
-    if (flags & PHI_HAS_GATE) { if (uniform_word(gate) == 0) return; }      // device-side predication (SPG line-search slots)
+    if (__builtin_expect((n_out_flags & PHI_HAS_GATE) != 0, 0)) { if (uniform_word(gate) == 0) return; }      // device-side predication (SPG line-search slots)
     if (chunk >= ncpo) return;
-    // where the fold expects this chunk's partials: output-major chunk numbering, or the regular rows' slots (one structure for
-    // all outputs).  In flight until the stores; both early exits are scalar branches without a wait of their own, so the load
-    // loses nothing behind them.
-    const int32_t slot_ld = uniform_word(pslot ? pslot + chunk : reinterpret_cast<const int32_t *>(cols));
-    const uint32_t CH = (uint32_t)iters * 256u;
     const char *cb = reinterpret_cast<const char *>(cols + (uint64_t)chunk * CH);
-    // output o0 + oo, clamped to the last one: each base is the one before it plus one output's entries, or the same again
-    const uint64_t per_out = (uint64_t)ncpo * CH;
-    const char *vb[OB];
-    vb[0] = reinterpret_cast<const char *>(vals + (uint64_t)(o0 * ncpo + chunk) * CH);
-#pragma unroll
-    for (int oo = 1; oo < OB; oo++) vb[oo] = vb[oo - 1] + (o0 + oo < (uint32_t)n_out ? per_out * sizeof(double) : 0);
-    // this lane's results after wave_sum_multi: which output, and whether this lane stores it
     constexpr int NR = wave_sum_multi_regs(OB);
-    uint32_t on[NR];
+    // bases of the outputs o0 + oo; the first one here, the others behind the issue of its loads
+    PhiStream vb[OB];
+    vb[0] = (PhiStream)(vals + (uint64_t)(blockIdx.y * OB * ncpo + chunk) * CH);
+    // this lane's results after wave_sum_multi: the position of its partial but for the slot, in double2, and whether it stores one
+    uint32_t opos[NR];
     bool mine[NR];
-#pragma unroll
-    for (int j = 0; j < NR; j++) {
-        on[j] = o0 + wave_sum_multi_index<OB>(lane, j);
-        mine[j] = wave_sum_multi_owner<OB>(lane) && on[j] < (uint32_t)n_out;
-    }
     const double *mc = m;
+    double s[OB];
+#pragma unroll
+    for (int oo = 0; oo < OB; oo++) s[oo] = 0.0;
+    double amax = 0.0;
+    uint32_t vo = lane * 32u, co = lane * (uint32_t)(4 * sizeof(COLT));
+    uint32_t iters = 1;
+    int32_t slot_ld = 0;
+    // one 256-block of the chunk; first: the sweep that opens the kernel, with the loop-invariant work behind the issue of its loads
+    auto sweep = [&](auto first) {
+        constexpr bool FIRST = decltype(first)::value;
+        const int4 cc = load_cols4<COLT>(reinterpret_cast<const COLT *>(cb + co));
+        double2 v01[OB], v23[OB];
+        v01[0] = stream_pair(vb[0] + vo);
+        v23[0] = stream_pair(vb[0] + vo + 16);
+        if constexpr (FIRST) {
+            phi_issue_point();
+            // output o0 + oo, clamped to the last one: each base is the one before it plus one output's values, or the same again
+            const uint32_t n_out = n_out_flags & PHI_N_OUT_MASK, o0 = blockIdx.y * OB;
+#pragma unroll
+            for (int oo = 1; oo < OB; oo++) vb[oo] = vb[oo - 1] + (o0 + oo < n_out ? per_out_bytes : 0);
+        }
+#pragma unroll
+        for (int oo = 1; oo < OB; oo++) {
+            v01[oo] = stream_pair(vb[oo] + vo);
+            v23[oo] = stream_pair(vb[oo] + vo + 16);
+            // (behind the loads of at most four outputs: the point orders the loads around it, and OB = 8 with all sixteen
+            //  in front of it takes 100 registers instead of 62)
+            if constexpr (FIRST) if (oo == (OB < 4 ? OB : 4) - 1) {
+                phi_issue_point();
+                const uint32_t n_out = n_out_flags & PHI_N_OUT_MASK, o0 = blockIdx.y * OB;
+                iters = CH >> 8;
+#pragma unroll
+                for (int j = 0; j < NR; j++) {
+                    opos[j] = o0 + wave_sum_multi_index<OB>(lane, j);
+                    mine[j] = wave_sum_multi_owner<OB>(lane) && opos[j] < n_out;
+                }
+                phi_late_args(m_stride, pstride, slots_per_output, partial);      // (one scalar wait)
+                // where the fold expects this chunk's partials: output-major chunk numbering, or the regular rows' slots (one
+                // structure for all outputs); a scalar load behind that wait, in flight until the stores
+                if (pslot) slot_ld = uniform_word(pslot + chunk);
+                const uint32_t ostride = pslot ? (uint32_t)uniform_value_here(slots_per_output) : ncpo;
+#pragma unroll
+                for (int j = 0; j < NR; j++) opos[j] *= ostride;
+                phi_issue_point();
+            }
+        }
+        const double m0 = mc[cc.x], m1 = mc[cc.y], m2 = mc[cc.z], m3 = mc[cc.w];
+        amax = fmax(fmax(amax, fmax(fabs(m0), fabs(m1))), fmax(fabs(m2), fabs(m3)));
+#pragma unroll
+        for (int oo = 0; oo < OB; oo++) {
+            s[oo] = fma(v01[oo].x, m0, s[oo]);
+            s[oo] = fma(v01[oo].y, m1, s[oo]);
+            s[oo] = fma(v23[oo].x, m2, s[oo]);
+            s[oo] = fma(v23[oo].y, m3, s[oo]);
+        }
+        vo += 2048u; co += (uint32_t)(256 * sizeof(COLT));
+    };
+    sweep(std::true_type());
     int64_t pdone = 0;      // candidates' partials in front of this one, in bytes
-    for (int c = 0; c < n_cand; c++) {
-        double s[OB];
-#pragma unroll
-        for (int oo = 0; oo < OB; oo++) s[oo] = 0.0;
-        double amax = 0.0;
-        uint32_t vo = lane * 32u, co = lane * (uint32_t)(4 * sizeof(COLT));
-        int it = 0;
-        do {      // (a chunk has at least one 256-block)
-            const int4 cc = load_cols4<COLT>(reinterpret_cast<const COLT *>(cb + co));
-            double2 v01[OB], v23[OB];
-#pragma unroll
-            for (int oo = 0; oo < OB; oo++) {
-                const double2 *vp = reinterpret_cast<const double2 *>(vb[oo] + vo);
-                v01[oo] = vp[0];
-                v23[oo] = vp[1];
-                // (behind the loads of at most four outputs: the statement orders the loads around it, and OB = 8 with all sixteen
-                //  in front of it takes 100 registers instead of 62)
-                if (oo == (OB < 4 ? OB : 4) - 1) phi_late_args(m_stride, pstride, slots_per_output, partial);
-            }
-            const double m0 = mc[cc.x], m1 = mc[cc.y], m2 = mc[cc.z], m3 = mc[cc.w];
-            amax = fmax(fmax(amax, fmax(fabs(m0), fabs(m1))), fmax(fabs(m2), fabs(m3)));
-#pragma unroll
-            for (int oo = 0; oo < OB; oo++) {
-                s[oo] = fma(v01[oo].x, m0, s[oo]);
-                s[oo] = fma(v01[oo].y, m1, s[oo]);
-                s[oo] = fma(v23[oo].x, m2, s[oo]);
-                s[oo] = fma(v23[oo].y, m3, s[oo]);
-            }
-            vo += 2048u; co += (uint32_t)(256 * sizeof(COLT));
-        } while (++it < iters);
+    uint32_t it = 1;
+    for (int c = 0;;) {
+        for (; it < iters; it++) sweep(std::false_type());
         double t[NR];
         wave_sum_multi<OB>(s, t);
         amax = wave_max_dpp(amax);
-        // (the slot word is a scalar load like the late arguments, so the wait for those, in the loop behind the issue of the
-        //  first stream loads, has brought it in too: no wait of its own is left here)
         const uint32_t slot = pslot ? (uint32_t)uniform_value_here(slot_ld) : chunk;
-        const uint32_t ostride = pslot ? (uint32_t)uniform_value_here(slots_per_output) : ncpo;
         char *pc = reinterpret_cast<char *>(uniform_value_here(partial)) + pdone;
 #pragma unroll
         for (int j = 0; j < NR; j++)
-            if (mine[j]) *reinterpret_cast<double2 *>(pc + (on[j] * ostride + slot) * 16u) = make_double2(t[j], amax);
+            if (mine[j]) store_partial(pc + (opos[j] + slot) * 16u, t[j], amax);
+        if (++c >= n_cand) break;
         mc += uniform_value_here(m_stride);      // (not hoisted in front of the loop, where they would be waited for)
         pdone += uniform_value_here(pstride) * (int64_t)sizeof(double2);
+        // (the next candidate's offsets taken as they are here: a chunk of one 256-block has the same columns for every candidate,
+        //  and their load is not to be moved in front of the loops)
+#pragma unroll
+        for (int oo = 0; oo < OB; oo++) s[oo] = 0.0;
+        amax = 0.0; it = 0;
+        vo = lane_value_here(lane * 32u); co = lane_value_here(lane * (uint32_t)(4 * sizeof(COLT)));
     }
 }
 
@@ -1647,7 +1707,9 @@ static int phi_ob(const bluest_plan_s *p, int n_cand)
 static void launch_chunks(bluest_plan_t p, const double *m, int n_cand, int64_t m_stride, hipStream_t st)
 {
     const int n_out = (int)p->outs.size();
-    const uint32_t flags = p->gate ? PHI_HAS_GATE : 0u;
+    // what the kernels' entry takes as it is: the entries of a chunk, and the top-bit flags next to n_out
+    const uint32_t CH = (uint32_t)p->iters * 256u;
+    const uint32_t n_out_flags = (uint32_t)n_out | (p->gate ? PHI_HAS_GATE : 0u);
     // one wavefront per workgroup of the chunk kernels (WPB = 1): single-wavefront workgroups drain earliest at the kernel's end
     // (same-box A/B at the headline size, two runs each: step 12.86 / 12.26 / 12.05 us with 4 / 2 / 1 wavefronts, 13.8 with 16)
     if (const int ob = phi_ob(p, n_cand)) {
@@ -1655,7 +1717,7 @@ static void launch_chunks(bluest_plan_t p, const double *m, int n_cand, int64_t 
         PhiObSet::dispatch(ob, [&](auto obc) {
             constexpr int OB = decltype(obc)::value;
 #define LCS2(COLT) hipLaunchKernelGGL((k_phi_chunks_shared<OB, 1, COLT>), dim3((unsigned)ncpo, (n_out + OB - 1) / OB), dim3(64), 0, st, \
-                                   p->d_vals, reinterpret_cast<const COLT *>(p->d_cols), m, p->d_pslot, p->iters, (uint32_t)ncpo, n_out, n_cand, flags, \
+                                   p->d_vals, reinterpret_cast<const COLT *>(p->d_cols), m, p->d_pslot, CH, (uint32_t)ncpo, (uint64_t)ncpo * CH * sizeof(double), n_out_flags, n_cand, \
                                    p->gate, m_stride, p->partial_stride, p->slots_per_output, p->d_partial)
             if (p->cols16) LCS2(uint16_t); else LCS2(int32_t);
 #undef LCS2
@@ -1663,7 +1725,7 @@ static void launch_chunks(bluest_plan_t p, const double *m, int n_cand, int64_t 
         return;
     }
 #define LPC(COLT) hipLaunchKernelGGL((k_phi_chunks<1, COLT>), dim3((unsigned)p->n_chunks), dim3(64), 0, st, p->d_vals, \
-                                  reinterpret_cast<const COLT *>(p->d_cols), m, p->d_pslot, p->iters, (uint32_t)p->n_chunks, n_out, n_cand, flags, \
+                                  reinterpret_cast<const COLT *>(p->d_cols), m, p->d_pslot, CH, (uint32_t)p->n_chunks, (uint64_t)0, n_out_flags, n_cand, \
                                   p->gate, m_stride, p->partial_stride, p->slots_per_output, p->d_partial)
     if (p->cols16) LPC(uint16_t); else LPC(int32_t);
 #undef LPC

@@ -4,7 +4,7 @@ Static instruction counts of the evaluation step's kernels from a device listing
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S -Iinclude -Ibluest_amd/csrc \
           -mllvm -amdgpu-kernarg-preload-count=16 bluest_amd/csrc/plan.hip -o plan.s      (the unit's flags of bluest_amd/build.py)
-    python tools/isa_counts.py plan.s
+    python tools/isa_counts.py plan.s [--paths]      (--paths: every instruction in front of the first stream / fold load)
 
 Per Phi kernel: all instructions of the listing (every block once -- which is what a wavefront executes when iters = 1 and
 n_cand = 1, minus the block a branch skips), split into VALU / SALU / VMEM / SMEM, the instructions in front of the first
@@ -101,16 +101,29 @@ def entry_report(name, body):
     first = next(i for i, x in enumerate(ins) if re.match(r"global_load_dwordx(2|4)", x))
     print(name)
     for i, x in enumerate(ins[:first + 1]):
-        if x.startswith(("s_load", "s_buffer_load", "global_load", "s_barrier", "s_waitcnt")):
+        if PATHS or x.startswith(("s_load", "s_buffer_load", "global_load", "s_barrier", "s_waitcnt")):
             print("   %5d  %s%s" % (i, x, "      <- first load of the stream" if i == first else ""))
+
+
+def first_fold_load(text):
+    """index of the regular fold's first partial load in a list of instructions: the rank_ab load (the kernel's first
+    global_load_ushort) belongs to the same row; the first 16-byte load behind it, or -- a kernel that issues the partials' loads in
+    front of it -- the earliest 16-byte load in front of it with no barrier and no LDS operation in between"""
+    ush = next(i for i, x in enumerate(text) if x.startswith("global_load_ushort"))
+    first = None
+    for i in range(ush - 1, -1, -1):
+        if text[i].startswith(("s_barrier", "ds_")):
+            break
+        if text[i].startswith("global_load_dwordx4"):
+            first = i
+    return first if first is not None else next(i for i in range(ush, len(text)) if text[i].startswith("global_load_dwordx4"))
 
 
 def solve_report(name, body):
     ins = instrs(body)
     print(name)
     barrier = [i for i, x in enumerate(ins) if x.startswith("s_barrier")]
-    ush = next(i for i, x in enumerate(ins) if x.startswith("global_load_ushort"))      # (the regular fold's rank_ab load)
-    fold = next(i for i in range(ush, len(ins)) if ins[i].startswith("global_load_dwordx4"))
+    fold = first_fold_load(ins)
     marks = [(fold, ins[fold] + "      <- first partial load of the regular fold")]
     for i, x in enumerate(ins):
         if x.startswith("s_load"):
@@ -167,14 +180,14 @@ def solve_regions(name, body, meta):
     """k_solve_grad in four regions.  (1) entry -> the regular fold's first partial load: the SHORTEST path through the kernel's
     blocks that meets no vector load, LDS operation or barrier on its way -- what a wavefront of a plan without a gate, with equal
     workgroups per output, no pads and no record executes.  (2) the fold: the text from that load to the barrier behind it, every
-    instruction once (all eight slot counts of the regular fold are in it; a wavefront runs one of them).  (3) between that barrier
+    instruction once (all eight slot counts of the regular fold are in it; a wavefront runs one of them; in a kernel that issues
+    the fold's loads at its entry the gate, line-search and pad-clearing blocks stand in it too).  (3) between that barrier
     and the next: the tile wavefronts' stream (up to the last 16-byte load) and the solving wavefront (the rest: every pass and
     rare path of solve_wave once).  (4) behind the second barrier: the tile wavefronts' forms and stores, all group sizes."""
     bl = blocks_of(body)
     flat = [(b, j) for b, (_, ins) in enumerate(bl) for j in range(len(ins))]
     text = [bl[b][1][j] for b, j in flat]
-    ush = next(i for i, x in enumerate(text) if x.startswith("global_load_ushort"))
-    first = next(i for i in range(ush, len(text)) if text[i].startswith("global_load_dwordx4"))
+    first = first_fold_load(text)
     tb, tj = flat[first]
     label_block = {lab: b for b, (labs, _) in enumerate(bl) for lab in labs}
     clean = lambda ins: not any(x.startswith(("global_", "flat_", "buffer_", "ds_", "s_barrier")) and      # noqa: E731
@@ -214,11 +227,10 @@ def solve_regions(name, body, meta):
             tally(head), ", ".join(x.replace("s_waitcnt ", "") for x in head if x.startswith("s_waitcnt")) or "none"))
         print("       loads, barriers and waits on that path (numbered along the path):")
         for i, x in enumerate(head):
-            if x.startswith(("s_load", "s_buffer_load", "global_load", "s_barrier", "s_waitcnt")):
+            if PATHS or x.startswith(("s_load", "s_buffer_load", "global_load", "s_barrier", "s_waitcnt")):
                 print("          %4d  %s" % (i, x))
-    bar = [i for i, x in enumerate(text) if x.startswith("s_barrier")]
-    b1 = next(i for i in bar if i > first)
-    b2 = next(i for i in bar if i > b1)
+    bar =[i for i, x in enumerate(text) if x.startswith("s_barrier")]
+    b1, b2 = bar[-2], bar[-1]      # (the kernel's last two barriers: behind the fold, and behind the solve; earlier ones belong to the gate and the pads)
     print("   (2) fold, first load -> barrier      %s" % tally(text[first:b1]))
     tl = max(i for i in range(b1, b2) if text[i].startswith("global_load_dwordx4"))
     print("   (3) tile stream behind the barrier   %s" % tally(text[b1 + 1:tl + 1]))
@@ -227,7 +239,12 @@ def solve_regions(name, body, meta):
     print("       whole kernel                     %s" % tally(text))
 
 
+PATHS = False      # --paths: every instruction in front of the first stream / fold load, not only the loads, barriers and waits
+
+
 def main():
+    global PATHS
+    PATHS = "--paths" in sys.argv[2:]
     lines = open(sys.argv[1]).read().split("\n")
     for name, prefix in PHI:
         _, body, meta = kernel_body(lines, prefix)
