@@ -110,6 +110,11 @@ SIGNATURES = {
     "bluest_field_op_shape": [c_vp, c_i64p, c_i64p, c_i64p],
     "bluest_field_op_destroy": [c_vp],
     "bluest_field_map": [c_i64, c_int, c_i64, c_vp, c_vp, c_vp, c_vp],
+    "bluest_field_accum_create": [c_int, c_i64, c_vp, ctypes.POINTER(c_vp), c_vp],
+    "bluest_field_accum_update": [c_vp, c_i64, c_vp, c_vp],
+    "bluest_field_accum_finish": [c_vp, c_i64p, c_vp, c_vp, c_vp, c_vp],
+    "bluest_field_accum_info": [c_vp, c_i64p],
+    "bluest_field_accum_destroy": [c_vp],
 }
 
 

@@ -11,8 +11,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["runtime.hip", "mirrors.hip", "plan.hip", "spg.hip", "intproj.hip", "xchg.hip", "newton.hip", "matfree.hip", "mfmc.hip", "mlmc.hip", "covproj.hip", "pilot.hip", "gsums.hip", "fields.hip", "moments.hip", "pilot4.hip", "field_moments.hip", "field_cov.hip", "field_pilot.hip", "field_map.hip", "wave_probe.hip"]     # translation units of libbluest_hip.so
-HEADERS = ["common.hpp", "solve.hpp", "plan.hpp", "spg_state.hpp", "jacobi.hpp", "subset_search.hpp", "staging.hpp", "slab_plan.hpp", "field_op_layout.hpp"]
+SOURCES = ["runtime.hip", "mirrors.hip", "plan.hip", "spg.hip", "intproj.hip", "xchg.hip", "newton.hip", "matfree.hip", "mfmc.hip", "mlmc.hip", "covproj.hip", "pilot.hip", "gsums.hip", "fields.hip", "moments.hip", "pilot4.hip", "field_moments.hip", "field_cov.hip", "field_pilot.hip", "field_map.hip", "field_accum.hip", "wave_probe.hip"]     # translation units of libbluest_hip.so
+HEADERS = ["common.hpp", "solve.hpp", "plan.hpp", "spg_state.hpp", "jacobi.hpp", "subset_search.hpp", "staging.hpp", "slab_plan.hpp", "field_op_layout.hpp", "field_partials.hpp"]
 # flags of single units.  plan.hip: the first 14 dwords of a kernel's arguments arrive in scalar registers with the wavefront (kernarg
 # preload; the step kernels' argument order is made for it, csrc/plan.hip).  BLUEST_EXTRA_HIPCC_FLAGS follows them on the command
 # line, so "-mllvm -amdgpu-kernarg-preload-count=0" there builds the same sources without it.

@@ -36,8 +36,13 @@
 // The shape never enters the order of the additions: z of a (row, component) is one chain whoever runs it, and every class is added
 // row by row from +0.0 by one thread.  Every value is read once; a chunk writes 2 d doubles.
 #include "staging.hpp"
+#include "field_partials.hpp"
 
 namespace {
+
+using bluest_partials::ZChunk;
+using bluest_partials::field_moments_rows;
+using bluest_partials::field_moments_split;
 
 constexpr int BLK = 256;                            // k_fmom_staged, k_fmom_fold
 constexpr int WIDE_COLS = WAVE;                     // components per workgroup of k_fmom_wide, and the least d it takes
@@ -52,28 +57,6 @@ static_assert(CLASSES * (WIDE_COLS - 1) <= 2 * BLK, "two passes of k_fmom_staged
 __host__ __device__ constexpr int padded_row(int W) { return W | 1; }
 __host__ __device__ constexpr int staged_doubles(int W, int d, int sb) { return sb * (padded_row(W) + d) + 2 * CLASSES * d; }
 static_assert((size_t)staged_doubles(BLUEST_MAX_MODELS * (WIDE_COLS - 1), WIDE_COLS - 1, 1) * 8 <= 64 * 1024, "one row of the widest staged segment fits the default LDS");
-
-// k_fmom_wide with a workgroup per class: where a chunk has fewer than 16 blocks of components and a workgroup would otherwise
-// read 1 MB and more on its own (the eight class sums that then go through memory are 1 / (8 L) of what the chunk reads)
-bool field_moments_split(int L, int64_t d) { return d >= WIDE_COLS && d < SPLIT_BELOW_D && L >= SPLIT_FROM_L; }
-
-// rows per sub-block of k_fmom_staged; 0: k_fmom_wide
-int field_moments_rows(int L, int64_t d)
-{
-    if (d >= WIDE_COLS) return 0;
-    int sb = GCHUNK;
-    while (sb > 1 && staged_doubles(L * (int)d, (int)d, sb) > STAGE_DOUBLES) sb >>= 1;
-    return sb;
-}
-
-struct ZChunk {
-    const double *src;      // row 0 of the chunk (device address)
-    const double *shift;    // the segment's first sample (device address): L d values
-    int64_t part;           // where the chunk's 2 d partial sums start, in doubles
-    int32_t rows, L;
-    int32_t col0;           // the segment's first coefficient
-    int32_t sb;             // field_moments_rows
-};
 
 struct ZSeg {
     int64_t part;           // first chunk's partial sums
@@ -307,6 +290,36 @@ __global__ __launch_bounds__(BLK) void k_fmom_fold(const ZSeg *__restrict__ segs
 
 }  // namespace
 
+// k_fmom_wide with a workgroup per class: where a chunk has fewer than 16 blocks of components and a workgroup would otherwise
+// read 1 MB and more on its own (the eight class sums that then go through memory are 1 / (8 L) of what the chunk reads)
+bool bluest_partials::field_moments_split(int L, int64_t d) { return d >= WIDE_COLS && d < SPLIT_BELOW_D && L >= SPLIT_FROM_L; }
+
+// rows per sub-block of k_fmom_staged; 0: k_fmom_wide
+int bluest_partials::field_moments_rows(int L, int64_t d)
+{
+    if (d >= WIDE_COLS) return 0;
+    int sb = GCHUNK;
+    while (sb > 1 && staged_doubles(L * (int)d, (int)d, sb) > STAGE_DOUBLES) sb >>= 1;
+    return sb;
+}
+
+int bluest_partials::field_moments_lds(int L, int64_t d)
+{
+    return d >= WIDE_COLS ? L * WIDE_COLS + 2 * WIDE_BLK : staged_doubles(L * (int)d, (int)d, field_moments_rows(L, d));
+}
+
+hipError_t bluest_partials::launch_fmom_partial(const ZChunk *table, size_t n, bool split, int lds_doubles, int64_t d, const double *coef,
+                                                double *part, hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    const size_t lds = (size_t)lds_doubles * 8;
+    const int64_t ncb = (d + WIDE_COLS - 1) / WIDE_COLS, nblk = (int64_t)n * ncb;
+    if (split) hipLaunchKernelGGL(k_fmom_wide<true>, dim3((unsigned)(nblk * CLASSES)), dim3(BLK), lds, st, table, coef, d, ncb, part);
+    else if (d >= WIDE_COLS) hipLaunchKernelGGL(k_fmom_wide<false>, dim3((unsigned)nblk), dim3(WIDE_BLK), lds, st, table, coef, d, ncb, part);
+    else hipLaunchKernelGGL(k_fmom_staged, dim3((unsigned)n), dim3(BLK), lds, st, table, coef, (int)d, part);
+    return hipGetLastError();
+}
+
 extern "C" int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t *counts, const int32_t *sizes,
                                              const double *const *values, const double *coef, double *zsum, double *zsq, void *stream)
 {
@@ -328,8 +341,6 @@ extern "C" int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t
         if (!std::isfinite(coef[t])) return fail(BLUEST_ERR_ARG, "coef[%lld]=%g is not finite", (long long)t, coef[t]);
     int rc = require_gpu(); if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool wide = d >= WIDE_COLS;
-
     // ---- the tables: segments ----
     std::vector<ZSeg> segs((size_t)S);
     std::vector<int64_t> col0((size_t)S), shift_at((size_t)S, -1);    // host segments: where the first-sample row [L d] lies in the shift buffer
@@ -380,7 +391,7 @@ extern "C" int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t
         const int L = sizes[s], sb = field_moments_rows(L, d);
         const int64_t W = (int64_t)L * d, per_chunk = segs[s].split ? 2 * d * CLASSES : 2 * d;
         int &lds = lds_doubles[2 * g + (size_t)segs[s].split];
-        lds = std::max(lds, wide ? L * WIDE_COLS + 2 * WIDE_BLK : staged_doubles((int)W, (int)d, sb));
+        lds = std::max(lds, bluest_partials::field_moments_lds(L, d));
         for (int64_t a = 0; a < rows; a += GCHUNK)
             chunks.add(g, (size_t)segs[s].split, ZChunk{base + a * W, shift, segs[s].part + ((first_row + a) / GCHUNK) * per_chunk,
                                                         (int32_t)std::min<int64_t>(GCHUNK, rows - a), L, (int32_t)col0[s], sb});
@@ -400,14 +411,8 @@ extern "C" int bluest_field_weighted_moments(int64_t S, int64_t d, const int64_t
     auto launch_group = [&](size_t g) -> hipError_t {
         for (size_t split = 0; split < 2; split++) {
             const size_t c0 = chunks.begin(g, split), c1 = chunks.end(g, split);
-            if (c1 <= c0) continue;
-            const size_t lds = (size_t)lds_doubles[2 * g + split] * 8;
-            const ZChunk *table = d_chunks + c0;
-            const int64_t nblk = (int64_t)(c1 - c0) * ncb;
-            if (split) hipLaunchKernelGGL(k_fmom_wide<true>, dim3((unsigned)(nblk * CLASSES)), dim3(BLK), lds, st, table, d_coef, d, ncb, d_part);
-            else if (wide) hipLaunchKernelGGL(k_fmom_wide<false>, dim3((unsigned)nblk), dim3(WIDE_BLK), lds, st, table, d_coef, d, ncb, d_part);
-            else hipLaunchKernelGGL(k_fmom_staged, dim3((unsigned)(c1 - c0)), dim3(BLK), lds, st, table, d_coef, (int)d, d_part);
-            const hipError_t e = hipGetLastError();
+            const hipError_t e = bluest_partials::launch_fmom_partial(d_chunks + c0, c1 - c0, split != 0, lds_doubles[2 * g + split], d, d_coef,
+                                                                      d_part, st);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;

@@ -25,8 +25,11 @@
 // The segments' checks, the slabs of staged host data, the chunk table and the slab loop of bluest_field_sums are those of
 // staging.hpp; bluest_field_stats has one array and cuts it into slabs of whole chunks itself.
 #include "staging.hpp"
+#include "field_partials.hpp"
 
 namespace {
+
+using bluest_partials::FChunk;
 
 constexpr int BLK = 256;
 constexpr int CHUNK = BLUEST_PILOT_CHUNK;
@@ -223,13 +226,6 @@ __global__ __launch_bounds__(BLK) void k_field_fold_comp(FieldShape sh, const in
 // ---- bluest_field_sums ---------------------------------------------------------------------------------------------------------
 constexpr int FOLD_COLS = 64;
 
-struct FChunk {
-    const double *src;      // row 0 of the chunk (device address)
-    int64_t part;           // where the chunk's W partial sums start, in doubles
-    int64_t W;              // column-components per row: sizes[s] * d
-    int32_t rows;
-};
-
 struct FSeg {
     int64_t part;           // first chunk's partial sums
     int64_t nchunks;
@@ -293,6 +289,14 @@ __global__ __launch_bounds__(BLK) void k_fsum_mu(int64_t d, const int64_t *__res
 }
 
 }  // namespace
+
+hipError_t bluest_partials::launch_fsum_partial(const FChunk *table, size_t n, int64_t Wmax, double *part, hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    const dim3 grid((unsigned)n, (unsigned)std::min<int64_t>((Wmax + BLK - 1) / BLK, 65535));
+    hipLaunchKernelGGL(k_fsum_partial, grid, dim3(BLK), 0, st, table, part);
+    return hipGetLastError();
+}
 
 extern "C" int bluest_field_stats(int64_t N, int L, int64_t d, const double *values, const double *w, double *sumse, double *sumsc,
                                   double *sumsd1, double *sumsd2, void *stream)
@@ -451,10 +455,7 @@ extern "C" int bluest_field_sums(int64_t S, int64_t d, const int64_t *counts, co
     const int64_t Wmax = (int64_t)Lmax * d;
     auto launch_group = [&](size_t g) -> hipError_t {
         const size_t c0 = chunks.begin(g), c1 = chunks.end(g);
-        if (c1 <= c0) return hipSuccess;
-        const dim3 grid((unsigned)(c1 - c0), (unsigned)std::min<int64_t>((Wmax + BLK - 1) / BLK, 65535));
-        hipLaunchKernelGGL(k_fsum_partial, grid, dim3(BLK), 0, st, (const FChunk *)d_chunks + c0, d_part);
-        return hipGetLastError();
+        return bluest_partials::launch_fsum_partial(d_chunks + c0, c1 - c0, Wmax, d_part, st);
     };
     rc = run_slabs(plan, dv + o_stage, values, counts, row_bytes.data(), 1, launch_group, st); if (rc) return rc;
     const dim3 gf((unsigned)S, (unsigned)std::min<int64_t>((Wmax + FOLD_COLS - 1) / FOLD_COLS, 65535));

@@ -136,17 +136,20 @@ def field_group_sums(values, weights=None, repeat_of=None, R=None, slab_bytes=SL
     return out if weights is None else (out, mu)
 
 
-def draw_field_values(problem, ls, N, widths, device_ok=False):
-    """this rank's share of N joint samples of the models `ls`, per output an array [share, len(ls), widths[n]]: the field-aware
-    sibling of bluest_amd._blue_fn.draw_values, with the same sequence of sampler / evaluate calls (bluest/blue_fn.py:106-129).
-    Ps[n][i] holds widths[n] components per sample: shape [d] for a batch of one, else [N2, d] (a number: N2 values).  With
-    `device_ok`, an evaluate that returns CUDA tensors keeps its batches on the device.
-    A problem may have a method _field_batch_hook(ls) (bluest_amd.field_maps.MappedFieldsMixin): it returns per output None, or
-    (the widths of the models `ls` themselves, a function from their len(ls) raw batches [N2, d_i] to [N2, len(ls), widths[n]]).
-    Such an output is checked for width and finiteness as it arrives and mapped, batch by batch, before it is kept."""
+def field_share(problem, N):
+    """how many of N joint samples this rank draws"""
     comm = problem.get_comm()
     size, rank = comm.Get_size(), comm.Get_rank()
-    mine = int(N) // size + (1 if rank < int(N) % size else 0)
+    return int(N) // size + (1 if rank < int(N) % size else 0)
+
+
+def field_batches(problem, ls, N, widths, device_ok=False):
+    """this rank's share of N joint samples of the models `ls`, one batch at a time: yields per batch the list over the outputs of
+    [N2, len(ls), widths[n]], numpy arrays or -- with `device_ok`, where evaluate returns CUDA tensors -- CUDA float64 tensors.
+    A batch is shaped, checked for finiteness, drawn again where a value is not finite, and mapped through _field_batch_hook
+    before it is handed out; nothing of it is kept here once the next one is asked for.  The sampler / evaluate calls are those of
+    draw_field_values, which is this generator with every batch kept."""
+    mine = field_share(problem, N)
     batched = len(signature(problem.sampler).parameters) > 1
     N1 = int(problem.params["sample_batch_size"]) if batched else 1
     n_out, L = problem.n_outputs, len(ls)
@@ -163,7 +166,7 @@ def draw_field_values(problem, ls, N, widths, device_ok=False):
                                                 "output_operators()", d))
         return v.reshape(N2, d)
 
-    out, batches, done = None, [], 0
+    done = 0
     while done < mine:
         N2 = min(N1, mine - done)
         while True:
@@ -182,18 +185,43 @@ def draw_field_values(problem, ls, N, widths, device_ok=False):
                 break
             if problem.verbose:
                 print("Warning! Problem evaluation returned inf or NaN value. Resampling...", flush=True)
+        if not _on_gpu(Ps[0]):
+            batch = [np.empty((N2, L, widths[n])) for n in range(n_out)]
+            for n in range(n_out):
+                if raw[n] is not None:
+                    batch[n][:] = raw[n][1]([shaped(np.asarray(Ps[n][i], dtype=np.float64), n, i, N2) for i in range(L)])
+                    continue
+                for i in range(L):
+                    batch[n][:, i, :] = shaped(np.asarray(Ps[n][i], dtype=np.float64), n, i, N2)
+            Ps = batch
+            del batch
+        done += N2
+        samples = None
+        yield Ps
+        Ps = None                                                       # (the batch is the caller's alone from here on)
+
+
+def draw_field_values(problem, ls, N, widths, device_ok=False):
+    """this rank's share of N joint samples of the models `ls`, per output an array [share, len(ls), widths[n]]: the field-aware
+    sibling of bluest_amd._blue_fn.draw_values, with the same sequence of sampler / evaluate calls (bluest/blue_fn.py:106-129).
+    Ps[n][i] holds widths[n] components per sample: shape [d] for a batch of one, else [N2, d] (a number: N2 values).  With
+    `device_ok`, an evaluate that returns CUDA tensors keeps its batches on the device.
+    A problem may have a method _field_batch_hook(ls) (bluest_amd.field_maps.MappedFieldsMixin): it returns per output None, or
+    (the widths of the models `ls` themselves, a function from their len(ls) raw batches [N2, d_i] to [N2, len(ls), widths[n]]).
+    Such an output is checked for width and finiteness as it arrives and mapped, batch by batch, before it is kept."""
+    mine = field_share(problem, N)
+    n_out, L = problem.n_outputs, len(ls)
+    out, batches, done = None, [], 0
+    for Ps in field_batches(problem, ls, N, widths, device_ok=device_ok):
         if _on_gpu(Ps[0]):
             batches.append(Ps)
         else:
             if out is None:
                 out = [np.empty((mine, L, widths[n])) for n in range(n_out)]
+            N2 = Ps[0].shape[0]
             for n in range(n_out):
-                if raw[n] is not None:
-                    out[n][done:done + N2] = raw[n][1]([shaped(np.asarray(Ps[n][i], dtype=np.float64), n, i, N2) for i in range(L)])
-                    continue
-                for i in range(L):
-                    out[n][done:done + N2, i, :] = shaped(np.asarray(Ps[n][i], dtype=np.float64), n, i, N2)
-        done += N2
+                out[n][done:done + N2] = Ps[n]
+        done += int(Ps[0].shape[0])
     if batches:
         import torch
         if out is not None:

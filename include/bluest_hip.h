@@ -815,6 +815,49 @@ int bluest_field_pilot_moments(int64_t N, int L, int64_t d, const double *values
 int bluest_field_pilot_scratch(int64_t bytes, int64_t *previous);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Part 19 (it stands here, next to the parts whose bits it returns; Part 18 closes the header) -- a resumable accumulator for ONE
+ * segment of one field output: the rows arrive over many calls, in pieces of any sizes, and are never all held.  finish returns
+ *   sums (L x d)            the bits of bluest_field_sums on the concatenated rows as one segment of sizes = L;
+ *   zsum, zsq (d each)      with coef (host, L finite scalars) given at creation: the bits of bluest_field_weighted_moments on
+ *                           the same segment with the same coefficients.  Without coef both must be null, and the moment
+ *                           kernels are never launched;
+ *   count                   the number of rows taken.
+ * update: values rows x L x d row-major float64, a host OR a device pointer per call (detected as in Part 10), 8-byte aligned;
+ * rows may be 0.  Host outputs, float64.
+ * THE STATE, on the device, owned by the handle, about 192 rows' worth of the segment whatever its length: the 64 lane partials
+ * of step 3 of Part 11 per column-component ([64][L d]) and, with coef, per sum of Part 15 ([64][2 d]); the segment's first row
+ * ([L d], Part 15's shift); the rows of the unfinished chunk (at most BLUEST_GSUM_CHUNK - 1 wait there between calls); and a
+ * scratch for one update -- the per-chunk partials, the chunk tables, the staging buffer of a host batch -- that only grows, so
+ * a steady run of equal batches does not allocate.
+ * THE ORDER.  The rows of the segment are cut into the chunks of Part 11 whatever the pieces are: a chunk that straddles two
+ * updates is completed inside the tail buffer and read from there, the whole chunks of a device batch are read where they lie,
+ * those of a host batch pass through the staging buffer in slabs of whole chunks under the budget of bluest_group_sums_slab, and
+ * the rows left over wait in the tail; finish takes them as the last, short chunk.  A chunk's value is formed by the kernels of
+ * Parts 12 and 15 from its own rows (and the first row): steps 1 and 2.  The chunks of an update have the global numbers c0 ..
+ * c0 + nc - 1; lane l takes its partial, adds the values of the chunks c = l (mod 64) among them in ascending c, and stores it.
+ * finish runs the tree of step 3 (off = 32, 16, 8, 4, 2, 1) over the 64 lane partials.
+ * WHY THE BITS ARE THOSE OF THE ONE-SHOT CALLS.  There, lane l starts from +0.0 and adds the values of the chunks l, l + 64, ...
+ * in ascending order, then the tree runs.  Here the lane partial starts at +0.0 and continues the same additions of the same
+ * values in the same order, call after call, and the same tree follows.  Nothing else enters: not the sizes of the pieces, not
+ * host or device memory, not the alignment, not the staging budget.  No update at all gives count 0 and +0.0 everywhere; one row
+ * gives +0.0 in zsum and zsq.  NaN / Inf propagate as in the one-shot calls.  No atomics, nothing sized by the number of
+ * compute units.
+ * Every call synchronises on `stream` before it returns: a batch may be freed right after update.
+ * BLUEST_ERR_ARG, returned before anything changes: L outside 1..BLUEST_MAX_MODELS, d < 1, more than 2^31 - 1 column-components
+ * L d, a coefficient that is not finite, a null handle or out-pointer, rows < 0, null or misaligned values with rows > 0,
+ * exactly one of zsum / zsq, zsum given without coef or the reverse.  BLUEST_ERR_STATE: update or finish after finish.  Without a
+ * device BLUEST_ERR_NOGPU: there is no CPU path.  destroy takes a null handle.
+ * bluest_field_accum_info, for tests and tuning: info[0..7] = rows taken, chunks carried, rows waiting in the tail, device
+ * allocations made so far, launches of the sum kernel, launches of a moment kernel, device bytes held, finished.
+ * --------------------------------------------------------------------------------------------------------- */
+typedef struct bluest_field_accum bluest_field_accum;
+int bluest_field_accum_create(int L, int64_t d, const double *coef, bluest_field_accum **out, void *stream);
+int bluest_field_accum_update(bluest_field_accum *a, int64_t rows, const double *values, void *stream);
+int bluest_field_accum_finish(bluest_field_accum *a, int64_t *count, double *sums, double *zsum, double *zsq, void *stream);
+int bluest_field_accum_info(const bluest_field_accum *a, int64_t *info);
+int bluest_field_accum_destroy(bluest_field_accum *a);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Part 18 -- fields on per-model meshes: sparse maps B_l (q x d_l) that take the d_l components of model l into a space of q
  * components all models of an output share -- point evaluation, prolongation to the finest mesh, restriction to an observation
  * grid, evaluation at quadrature points.  After the map, Parts 12 and 15 to 17 apply as they are to the array [N, L, q].  (The
