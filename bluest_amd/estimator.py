@@ -110,6 +110,85 @@ def group_sums(values, weights=None, repeat_of=None, R=None, slab_bytes=SLAB_BYT
     return out if weights is None else (out, mu)
 
 
+def sampled_columns(out):
+    """the sampled groups of the allocation `out` (a MOSAP_output) in the order of the group list: [(g, models, first column, m_g)],
+    the first column counted over the columns of the sampled groups, as SamplingMixin._blue_weights() lays out W"""
+    samples = np.asarray(out["samples"])
+    cols, c = [], 0
+    for g in np.flatnonzero(samples > 0).tolist():
+        ls = [int(l) for l in out["flattened_groups"][g]]
+        cols.append((g, ls, c, int(samples[g])))
+        c += len(ls)
+    return cols
+
+
+def flushed_draws(problem, n_rep, cols, slab_bytes, draw, flush):
+    """the draw / flush loop of every _sample_estimators: per repeat each of the sampled groups `cols` (sampled_columns) is drawn
+    in the order of the group list, share, nbytes = draw(col): this rank's values as they go to the gather, and the bytes the
+    group counts for over all ranks (so that every rank flushes at the same points).  Once `slab_bytes` are pending, and at the
+    end, the shares are gathered and rank 0 calls flush(pending, shares): pending[i] = (repeat, col), shares[rank][i].  A flush
+    never splits a group; it may begin or end inside a repeat."""
+    comm = problem.get_comm()
+    pending = []                                                        # (repeat, col, this rank's share)
+
+    def flush_pending():
+        if pending:
+            shares = comm.gather([p[2] for p in pending], root=0)      # [rank][segment]
+            if comm.Get_rank() == 0:
+                flush([p[:2] for p in pending], shares)
+            del pending[:]
+
+    held = 0
+    for r in range(n_rep):
+        for col in cols:
+            share, nbytes = draw(col)
+            pending.append((r, col, share))
+            held += nbytes
+            if held >= slab_bytes:
+                flush_pending()
+                held = 0
+    flush_pending()
+
+
+def collecting_solve(problem, solve, attribute, empty, args):
+    """(solve(**args), what the flush hooks filed meanwhile): `attribute` of the problem is `empty` while the solve runs and None
+    again afterwards, whatever happens; what rank 0 collected is broadcast"""
+    setattr(problem, attribute, empty)
+    try:
+        result = solve(**args)
+        taken = getattr(problem, attribute)
+    finally:
+        setattr(problem, attribute, None)
+    comm = problem.get_comm()
+    return result, comm.bcast(taken if comm.Get_rank() == 0 else None, root=0)
+
+
+def sampled_errors(problem, source, sampled, share, promised=True):
+    """[n_outputs]: sqrt(sum_g m_g share(moments, n, g, ls, w)) over the sampled groups g of every output n whose BLUE weights w of
+    the group's columns are not all zero; moments = sampled() is what the last solve() collected (it raises where there is
+    nothing).  source="model" gives sqrt(Vs) of solve() again -- with `promised` straight from _blue_weights(), else from the
+    same sum.  Rank 0 computes, every rank returns."""
+    if source not in ("samples", "model"):
+        raise ValueError("source must be 'samples' or 'model'")
+    moments = sampled()
+    comm = problem.get_comm()
+    errs = None
+    if comm.Get_rank() == 0:
+        W, Vs = problem._blue_weights()
+        if source == "model" and promised:
+            errs = np.sqrt(np.asarray(Vs, dtype=np.float64))
+        else:
+            var = np.zeros(problem.n_outputs)
+            for g, ls, c, m in sampled_columns(problem.MOSAP_output):
+                for n in range(problem.n_outputs):
+                    w = W[n, c:c + len(ls)]
+                    if not w.any():                                     # the group is not in this output's mapping
+                        continue
+                    var[n] += m * share(moments, n, g, ls, w)
+            errs = np.sqrt(var)
+    return comm.bcast(errs, root=0)
+
+
 class SamplingMixin(object):
     reorder_graph_nodes = reorder_all_graph_nodes = BLUEProblem._out_of_scope      # named here so that they refuse with a message
 
@@ -154,11 +233,9 @@ class SamplingMixin(object):
             return cached[1]
         mos = self.MOSAP
         samples = np.asarray(out["samples"])
-        chosen = np.flatnonzero(samples > 0)
-        where = {int(g): i for i, g in enumerate(chosen)}
-        sizes = [len(out["flattened_groups"][g]) for g in chosen]
-        col0 = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        W, Vs = np.zeros((self.n_outputs, int(col0[-1]))), []
+        cols = sampled_columns(out)
+        col0 = {g: c for g, _, c, _ in cols}
+        W, Vs = np.zeros((self.n_outputs, sum(len(ls) for _, ls, _, _ in cols))), []
         for n in range(self.n_outputs):
             sap, mp = mos.SAPS[n], np.asarray(mos.mappings[n])
             m = samples[mp].astype(np.float64)
@@ -175,7 +252,7 @@ class SamplingMixin(object):
                 blocks = np.asarray(sap.invcovs[k - 1]).reshape(-1, k, k)[hit]                # (h, k, k) = C_g^-1
                 w = np.einsum("hjs,hj->hs", blocks, v[members])
                 for row, i in zip(w, hit.tolist()):
-                    c = int(col0[where[int(mp[lo + i])]])
+                    c = col0[int(mp[lo + i])]
                     W[n, c:c + k] = row
         result = (W, np.array(Vs))
         self._blue_weights_cache = (out, result)
@@ -192,44 +269,29 @@ class SamplingMixin(object):
         over all ranks, so that every rank flushes at the same points), the parts of mu added in order."""
         comm = self.get_comm()
         rank = comm.Get_rank()
-        out = self.MOSAP_output
-        samples = np.asarray(out["samples"])
-        chosen = np.flatnonzero(samples > 0)
-        groups = [out["flattened_groups"][g] for g in chosen]
-        for ls in groups:
+        cols = sampled_columns(self.MOSAP_output)
+        for _, ls, _, _ in cols:
             self._check_width(len(ls))
         W = self._blue_weights()[0] if rank == 0 else None
-        width = [len(ls) for ls in groups]
-        first_col = np.cumsum([0] + width[:-1]).tolist()
         mus = np.zeros((n_rep, self.n_outputs))
-        pending = []                                                    # (repeat, position of the group, this rank's values)
 
-        def flush():
-            if not pending:
-                return
-            shares = comm.gather([p[2] for p in pending], root=0)      # [rank][segment]
-            if rank == 0:
-                first, last = pending[0][0], pending[-1][0]
-                # a flush may begin or end inside a repeat: every segment brings the weights of its own group
-                weights = np.concatenate([W[:, first_col[gi]:first_col[gi] + width[gi]] for _, gi, _ in pending], axis=1)
-                joined = [self._joined([share[i] for share in shares]) for i in range(len(pending))]
-                self._segments_flushed([(r, int(chosen[gi])) for r, gi, _ in pending], joined)
-                _, part = group_sums(joined, weights=weights, repeat_of=[r - first for r, _, _ in pending], R=last - first + 1)
-                mus[first:last + 1] += part
-            del pending[:]
+        def draw(col):
+            _, ls, _, m = col
+            mine = draw_values(self, ls, m, device_ok=True)
+            if comm.Get_size() > 1 and hasattr(mine, "data_ptr"):
+                mine = mine.cpu().numpy()
+            return mine, m * len(ls) * self.n_outputs * 8
 
-        held = 0
-        for r in range(n_rep):
-            for gi, (ls, g) in enumerate(zip(groups, chosen)):
-                mine = draw_values(self, ls, int(samples[g]), device_ok=True)
-                if comm.Get_size() > 1 and hasattr(mine, "data_ptr"):
-                    mine = mine.cpu().numpy()
-                pending.append((r, gi, mine))
-                held += int(samples[g]) * len(ls) * self.n_outputs * 8
-                if held >= SLAB_BYTES:
-                    flush()
-                    held = 0
-        flush()
+        def flush(pending, shares):
+            first, last = pending[0][0], pending[-1][0]
+            # every segment brings the weights of its own group
+            weights = np.concatenate([W[:, c:c + len(ls)] for _, (_, ls, c, _) in pending], axis=1)
+            joined = [self._joined([share[i] for share in shares]) for i in range(len(pending))]
+            self._segments_flushed([(r, col[0]) for r, col in pending], joined)
+            _, part = group_sums(joined, weights=weights, repeat_of=[r - first for r, _ in pending], R=last - first + 1)
+            mus[first:last + 1] += part
+
+        flushed_draws(self, n_rep, cols, SLAB_BYTES, draw, flush)
         return comm.bcast(mus if rank == 0 else None, root=0)
 
     def solve(self, K=4, budget=None, eps=None, groups=None, multi_groups=None, solver=None, verbose=True, continuous_relaxation=False,

@@ -49,9 +49,9 @@ import numpy as np
 
 from . import _lib
 from .blue_models import BLUEProblem
-from .estimator import SLAB_BYTES, SamplingMixin
+from .estimator import SLAB_BYTES, collecting_solve, sampled_errors
 from .fields import FieldOutputsMixin, _field_segment_table
-from .moments import _triangle
+from .moments import _triangles_by_width, pool_covariances
 from .sap import BLUESTError
 
 
@@ -77,16 +77,13 @@ def field_group_moments(values, w, with_first=False, slab_bytes=SLAB_BYTES):
 
 
 def _unpacked(counts, sizes, second, cross, first=None):
-    """the outputs of Part 16 ([P], [P] and [T, d] over all segments) as a list of (N, second [L, L], cross [L, L][, first [L, d]]).
-    The packed triangles become full matrices width by width, not segment by segment, as moments._unpacked does."""
+    """the outputs of Part 16 ([P], [P] and [T, d] over all segments) as a list of (N, second [L, L], cross [L, L][, first [L, d]]),
+    the triangles made full width by width as moments._unpacked does"""
     sizes = sizes.astype(np.int64)
-    tri = sizes * (sizes + 1) // 2
-    col0, pair0 = np.cumsum(sizes) - sizes, np.cumsum(tri) - tri
+    col0 = np.cumsum(sizes) - sizes
     out = [None] * len(sizes)
     counts = counts.tolist()
-    for L in set(sizes.tolist()):
-        which = np.flatnonzero(sizes == L)
-        at = pair0[which][:, None, None] + _triangle(L)                                         # [segment, L, L]
+    for L, which, at in _triangles_by_width(sizes):
         for s, m2, mx in zip(which.tolist(), np.ascontiguousarray(second[at]), np.ascontiguousarray(cross[at])):
             out[s] = (counts[s], m2, mx) + (() if first is None else (first[col0[s]:col0[s] + L].copy(),))
     return out
@@ -109,12 +106,6 @@ class FieldCovariancesMixin(object):
     field_sample_covariances = None
     _collecting_covariances = None
 
-    def _field_covariances_refused(self):
-        """no declared weights on the GPU path: without SamplingMixin the parent's host flow draws the samples, and an inner
-        product written in Python is not a weight vector"""
-        return (not isinstance(self, SamplingMixin) or not isinstance(self, FieldOutputsMixin)
-                or type(self).get_models_inner_products is not FieldOutputsMixin.get_models_inner_products)
-
     def _field_segments_flushed(self, where, n, segments):
         if self._collecting_covariances is not None:                    # (a variance test's repeats are not looked at)
             ws, _ = self._field_weights()
@@ -128,20 +119,14 @@ class FieldCovariancesMixin(object):
         args = dict(K=K, budget=budget, eps=eps, groups=groups, multi_groups=multi_groups, solver=solver, verbose=verbose,
                     continuous_relaxation=continuous_relaxation, max_model_samples=max_model_samples,
                     optimization_solver_params=optimization_solver_params)
-        if self._field_covariances_refused():
+        if FieldOutputsMixin._sampled_moments_refused(self):
             return super().solve(**args)
-        self._collecting_covariances = [{} for _ in range(self.n_outputs)]
-        try:
-            result = super().solve(**args)
-            covs = self._collecting_covariances
-        finally:
-            self._collecting_covariances = None
-        comm = self.get_comm()
-        self.field_sample_covariances = comm.bcast(covs if comm.Get_rank() == 0 else None, root=0)
+        result, self.field_sample_covariances = collecting_solve(self, super().solve, "_collecting_covariances",
+                                                                 [{} for _ in range(self.n_outputs)], args)
         return result
 
     def _field_covariances_sampled(self):
-        if self._field_covariances_refused():
+        if FieldOutputsMixin._sampled_moments_refused(self):
             raise BLUESTError("sampled field covariances need SamplingMixin and FieldOutputsMixin among the bases and declared "
                               "output_weights(), not inner products written in Python")
         if self.field_sample_covariances is None or self.MOSAP_output is None:
@@ -152,47 +137,12 @@ class FieldCovariancesMixin(object):
         """[n_outputs]: sqrt(sum_g m_g u_g' C_g u_g) over the sampled groups g, u_g the BLUE weights of the group's columns and C_g
         the covariance of the group's samples in the inner product (source="samples"; the model's block where the group was drawn
         once), or sqrt(Vs) of solve() again (source="model")"""
-        if source not in ("samples", "model"):
-            raise ValueError("source must be 'samples' or 'model'")
-        covs = self._field_covariances_sampled()
-        comm = self.get_comm()
-        errs = None
-        if comm.Get_rank() == 0:
-            W, Vs = self._blue_weights()
-            if source == "model":
-                errs = np.sqrt(np.asarray(Vs, dtype=np.float64))
-            else:
-                out = self.MOSAP_output
-                samples = np.asarray(out["samples"])
-                var, c = np.zeros(self.n_outputs), 0
-                for g in np.flatnonzero(samples > 0).tolist():
-                    ls = [int(l) for l in out["flattened_groups"][g]]
-                    for n in range(self.n_outputs):
-                        u = W[n, c:c + len(ls)]
-                        if not u.any():                                 # the group is not in this output's mapping
-                            continue
-                        N, C_hat = covs[n][g]
-                        C = C_hat if N >= 2 else np.asarray(self.get_covariance(n))[np.ix_(ls, ls)]
-                        var[n] += int(samples[g]) * float(u @ C @ u)
-                    c += len(ls)
-                errs = np.sqrt(var)
-        return comm.bcast(errs, root=0)
+        def share(covs, n, g, ls, u):
+            N, C_hat = covs[n][g]
+            C = C_hat if N >= 2 else np.asarray(self.get_covariance(n))[np.ix_(ls, ls)]
+            return float(u @ C @ u)
+        return sampled_errors(self, source, self._field_covariances_sampled, share)
 
     def pooled_covariances(self):
-        """(Cs, dof), per output M x M: dof[i, j] = sum of N_g - 1 over the sampled groups with N_g >= 2 that hold both i and j,
-        Cs[i, j] = sum (N_g - 1) C^_g[i, j] / dof[i, j] where dof > 0, elsewhere the entry of get_covariance(n) (NaN included)"""
-        covs = self._field_covariances_sampled()
-        groups = self.MOSAP_output["flattened_groups"]
-        Cs, dofs = [], []
-        for n in range(self.n_outputs):
-            acc, dof = np.zeros((self.M, self.M)), np.zeros((self.M, self.M))
-            for g, (N, C_hat) in sorted(covs[n].items()):
-                if N >= 2:
-                    ix = np.ix_(groups[g], groups[g])
-                    acc[ix] += (N - 1) * C_hat
-                    dof[ix] += N - 1
-            C = np.array(self.get_covariance(n), dtype=np.float64)
-            C[dof > 0] = acc[dof > 0] / dof[dof > 0]
-            Cs.append(C)
-            dofs.append(dof)
-        return Cs, dofs
+        """(Cs, dof) with MomentsMixin's definition, entry for entry, in the outputs' inner products"""
+        return pool_covariances(self, self._field_covariances_sampled())

@@ -45,7 +45,7 @@ import numpy as np
 
 from . import _lib
 from .blue_models import BLUEProblem
-from .estimator import SLAB_BYTES, SamplingMixin
+from .estimator import SLAB_BYTES, collecting_solve, sampled_columns, sampled_errors
 from .fields import FieldOutputsMixin, _field_segment_table
 from .sap import BLUESTError
 
@@ -80,27 +80,10 @@ class FieldErrorsMixin(object):
     field_sample_moments = None
     _collecting_fields = None
 
-    def _field_errors_refused(self):
-        """no declared weights on the GPU path: without SamplingMixin the parent's host flow draws the samples, and an inner
-        product written in Python is not a weight vector"""
-        return (not isinstance(self, SamplingMixin) or not isinstance(self, FieldOutputsMixin)
-                or type(self).get_models_inner_products is not FieldOutputsMixin.get_models_inner_products)
-
-    def _sampled_columns(self):
-        """the sampled groups of the current allocation in the order of the group list: [(g, models, first column, m_g)]"""
-        out = self.MOSAP_output
-        samples = np.asarray(out["samples"])
-        cols, c = [], 0
-        for g in np.flatnonzero(samples > 0).tolist():
-            ls = [int(l) for l in out["flattened_groups"][g]]
-            cols.append((g, ls, c, int(samples[g])))
-            c += len(ls)
-        return cols
-
     def _field_segments_flushed(self, where, n, segments):
         if self._collecting_fields is not None:                         # (a variance test's repeats are not looked at)
             W = self._blue_weights()[0]
-            col0 = {g: (c, len(ls)) for g, ls, c, _ in self._sampled_columns()}
+            col0 = {g: (c, len(ls)) for g, ls, c, _ in sampled_columns(self.MOSAP_output)}
             coef = np.concatenate([W[n, col0[g][0]:col0[g][0] + col0[g][1]] for _, g in where])
             for (_, g), (N, zsum, zsq) in zip(where, field_weighted_moments(segments, coef)):
                 self._collecting_fields[n][g] = (N, variance_of(N, zsum, zsq))
@@ -111,20 +94,14 @@ class FieldErrorsMixin(object):
         args = dict(K=K, budget=budget, eps=eps, groups=groups, multi_groups=multi_groups, solver=solver, verbose=verbose,
                     continuous_relaxation=continuous_relaxation, max_model_samples=max_model_samples,
                     optimization_solver_params=optimization_solver_params)
-        if self._field_errors_refused():
+        if FieldOutputsMixin._sampled_moments_refused(self):
             return super().solve(**args)
-        self._collecting_fields = [{} for _ in range(self.n_outputs)]
-        try:
-            result = super().solve(**args)
-            moments = self._collecting_fields
-        finally:
-            self._collecting_fields = None
-        comm = self.get_comm()
-        self.field_sample_moments = comm.bcast(moments if comm.Get_rank() == 0 else None, root=0)
+        result, self.field_sample_moments = collecting_solve(self, super().solve, "_collecting_fields",
+                                                             [{} for _ in range(self.n_outputs)], args)
         return result
 
     def _field_sampled(self):
-        if self._field_errors_refused():
+        if FieldOutputsMixin._sampled_moments_refused(self):
             raise BLUESTError("sampled field errors need SamplingMixin and FieldOutputsMixin among the bases and declared "
                               "output_weights(), not inner products written in Python")
         if self.field_sample_moments is None or self.MOSAP_output is None:
@@ -139,27 +116,11 @@ class FieldErrorsMixin(object):
         """[n_outputs]: sqrt(sum_g m_g sum_c w_c var_g[c]) over the sampled groups g, var_g the sampled variance of the group's
         weighted combination z (source="samples"; the model's share u' C u where the group was drawn once), or sqrt(Vs) of solve()
         again (source="model")"""
-        if source not in ("samples", "model"):
-            raise ValueError("source must be 'samples' or 'model'")
-        moments = self._field_sampled()
-        comm = self.get_comm()
-        errs = None
-        if comm.Get_rank() == 0:
-            W, Vs = self._blue_weights()
-            if source == "model":
-                errs = np.sqrt(np.asarray(Vs, dtype=np.float64))
-            else:
-                ws, _ = self._field_weights()
-                var = np.zeros(self.n_outputs)
-                for g, ls, c, m in self._sampled_columns():
-                    for n in range(self.n_outputs):
-                        w = W[n, c:c + len(ls)]
-                        if not w.any():                                 # the group is not in this output's mapping
-                            continue
-                        N, v = moments[n][g]
-                        var[n] += m * (float(np.dot(ws[n], v)) if N >= 2 else self._model_share(n, ls, w))
-                errs = np.sqrt(var)
-        return comm.bcast(errs, root=0)
+        def share(sampled, n, g, ls, w):
+            moments, ws = sampled
+            N, v = moments[n][g]
+            return float(np.dot(ws[n], v)) if N >= 2 else self._model_share(n, ls, w)
+        return sampled_errors(self, source, lambda: (self._field_sampled(), self._field_weights()[0]), share)
 
     def sampled_error_fields(self):
         """(maps, unsampled): maps[n][c] = sqrt(sum_g m_g var_g[c]) over the groups drawn at least twice, an ndarray [d_n] or the
@@ -172,7 +133,7 @@ class FieldErrorsMixin(object):
             W = self._blue_weights()[0]
             ws, is_field = self._field_weights()
             maps, unsampled = [np.zeros(len(w)) for w in ws], [0.0] * self.n_outputs
-            for g, ls, c, m in self._sampled_columns():
+            for g, ls, c, m in sampled_columns(self.MOSAP_output):
                 for n in range(self.n_outputs):
                     w = W[n, c:c + len(ls)]
                     if not w.any():

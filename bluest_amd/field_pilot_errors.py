@@ -53,10 +53,9 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .blue_models import BLUEProblem
 from .estimator import SLAB_BYTES
 from .fields import FieldOutputsMixin, _segment, _stream_of, field_statistics
-from .pilot_errors import PilotErrorsMixin, next_pilot_size
+from .pilot_errors import _GrowingPilot
 from .sap import BLUESTError
 
 BLUEST_FIELD_STRIP = 512             # include/bluest_hip.h, Part 17
@@ -122,17 +121,11 @@ def field_pilot_standard_errors(N, qs1, qs2, rs1=None, rs2=None):
     return se_c, se_d
 
 
-class FieldPilotErrorsMixin(object):
-    reorder_graph_nodes = reorder_all_graph_nodes = BLUEProblem._out_of_scope      # named here so that they refuse with a message
-    pilot_report = None
-    _pilot_errors = None                 # (errors of C [n_outputs, M, M], errors of dV [n_outputs, M, M])
-    _pilot_kept = None                   # rank 0, while the pilot runs: per output the values drawn so far [N, L, d_n]
-    _pilot_have = 0                      # every rank: how many samples the values kept on rank 0 hold
+class FieldPilotErrorsMixin(_GrowingPilot):
+    _pilot_needs = "the per-sample inner products of declared weights"
     _pilot_sumse = None                  # the sums of the components the last _pilot_sums returned
 
-    _pilot_tol = PilotErrorsMixin._pilot_tol
-
-    def _no_field_moments(self):
+    def _pilot_unavailable(self):
         """why the per-sample inner products do not come from bluest_field_pilot_moments, or None"""
         if not isinstance(self, FieldOutputsMixin):
             return "FieldOutputsMixin is not among the bases"
@@ -140,19 +133,21 @@ class FieldPilotErrorsMixin(object):
             return "inner products written in Python are summed on the host"
         return None
 
-    # ---- BLUEProblem's hooks ----------------------------------------------------------------------------------------------------
-    def _init_inputs(self, C, costs):
-        why = self._no_field_moments()
-        if why is not None and self._pilot_tol() is not None:
-            raise BLUESTError("covariance_estimation_tol needs the per-sample inner products of declared weights: " + why)
-        return super()._init_inputs(C, costs)
+    def _pilot_caps(self, ls, N, size):
+        ws, _ = self._field_weights()
+        by_samples = max(N, int(self.params.get("covariance_estimation_max_samples", 64 * N)))
+        per_sample = len(ls) * max(len(w) for w in ws) * 8              # the kept values of the largest output
+        by_bytes = max(N, int(self.params.get("covariance_estimation_max_bytes", MAX_BYTES)) // per_sample // size * size)
+        return min(by_samples, by_bytes), "bytes" if by_bytes < by_samples else "samples"
 
-    def _init_from_datafile(self, datafile, costs):
-        if self._pilot_tol() is not None:
-            raise BLUESTError("covariance_estimation_tol needs pilot samples: a problem loaded from a model-graph file draws none")
-        return super()._init_from_datafile(datafile, costs)
+    def _pilot_reset(self):
+        super()._pilot_reset()
+        self._pilot_sumse = None
 
-    # ---- FieldOutputsMixin's hooks: a round draws what is missing, rank 0 keeps what was drawn ---------------------------------------
+    def _pilot_reported(self, samples, rounds, ratio, converged, cap):
+        return dict(super()._pilot_reported(samples, rounds, ratio, converged, cap), capped_by=cap)
+
+    # ---- FieldOutputsMixin's hooks: a round draws what is missing, rank 0 keeps what was drawn, per output [N, L, d_n] ----------------
     def _field_pilot_count(self, ls, N):
         return N - self._pilot_have
 
@@ -177,98 +172,17 @@ class FieldPilotErrorsMixin(object):
         self._pilot_sumse = sums[0]
         return sums
 
-    def estimate_missing_covariances(self, N):
-        """FieldOutputsMixin's estimate_missing_covariances, then the standard errors of what it estimated; with
-        params["covariance_estimation_tol"] the pilot grows from N samples until the errors meet the tolerance"""
-        if self._no_field_moments() is not None:
-            return super().estimate_missing_covariances(N)
-        unknown = [cp.linked & np.isnan(cp.cov) for cp in self._coupling]
-        ls = [int(l) for l in np.flatnonzero(np.logical_or.reduce(unknown).any(axis=1))]
-        no_dV = [~np.isfinite(np.array(d, dtype=np.float64)) for d in self.dV]
-        nan = lambda: np.full((self.n_outputs, self.M, self.M), np.nan)
-        if len(ls) == 0:                                                # nothing to estimate: nothing has an error
-            if self._pilot_errors is None:
-                self._pilot_errors = (nan(), nan())
-                self.pilot_report = dict(samples=0, rounds=0, ratio=None, converged=True, capped_by=None)
-            return
-        self._pilot_errors = (nan(), nan())
-        tol, comm = self._pilot_tol(), self.get_comm()
-        size, N = comm.Get_size(), int(N)
-        ws, _ = self._field_weights()
-        by_samples = max(N, int(self.params.get("covariance_estimation_max_samples", 64 * N)))
-        per_sample = len(ls) * max(len(w) for w in ws) * 8              # the kept values of the largest output
-        by_bytes = max(N, int(self.params.get("covariance_estimation_max_bytes", MAX_BYTES)) // per_sample // size * size)
-        N_max = min(by_samples, by_bytes)
-        before = ([cp.cov.copy() for cp in self._coupling], [np.array(d, dtype=np.float64) for d in self.dV])
-        rounds = 0
-        try:
-            while True:
-                for cp, cov in zip(self._coupling, before[0]):         # every round estimates from the inputs as they were given
-                    cp.cov[...] = cov
-                self.dV = [d.copy() for d in before[1]]
-                super().estimate_missing_covariances(N)
-                rounds += 1
-                self._pilot_have = N
-                found = None
-                if comm.Get_rank() == 0:
-                    found = self._pilot_round(ls, N, ws, unknown, no_dV, tol)
-                se_c, se_d, ratio = comm.bcast(found, root=0)
-                more = None
-                if comm.Get_rank() == 0:                                # rank 0 decides
-                    more = next_pilot_size(N, ratio, size, N_max) if tol is not None and ratio > 1 and N < N_max else N
-                more = comm.bcast(more, root=0)
-                if more == N:
-                    break
-                N = more
-        finally:
-            self._pilot_kept, self._pilot_have, self._pilot_sumse = None, 0, None
-        where = np.ix_(range(self.n_outputs), ls, ls)
-        self._pilot_errors[0][where] = se_c
-        self._pilot_errors[1][where] = se_d
-        for n in range(self.n_outputs):
-            self._pilot_errors[0][n][~unknown[n]] = np.nan              # given, not estimated
-            self._pilot_errors[1][n][~(no_dV[n] & np.triu(np.ones((self.M, self.M), dtype=bool), 1))] = np.nan
-        converged = tol is None or ratio <= 1
-        capped_by = None if converged else ("bytes" if by_bytes < by_samples else "samples")
-        self.pilot_report = dict(samples=N, rounds=rounds, ratio=float(ratio) if tol is not None else None, converged=converged,
-                                 capped_by=capped_by)
-        if not converged and comm.Get_rank() == 0:
-            print("WARNING! The pilot estimates miss covariance_estimation_tol = %g after %d samples (largest error / tolerance: "
-                  "%.3g). Raise covariance_estimation_max_%s." % (tol, N, ratio, capped_by))
-
-    def _pilot_round(self, ls, N, ws, unknown, no_dV, tol):
-        """rank 0: (SE(C^), SE(dV^)) [n_outputs, L, L] of the values kept, from one field_pilot_moments call per output centred at
-        the mean field_statistics returned, and the largest ratio of an error to what the tolerance allows over the estimated
-        coupled entries (0 without a tolerance)"""
+    def _pilot_round(self, ls, N, estimates):
+        """one field_pilot_moments call per output, centred at the mean field_statistics returned; C^ and dV^ are the means of the
+        per-sample inner products q_s and r_s"""
         L = len(ls)
+        ws, _ = self._field_weights()
         se_c, se_d = np.empty((self.n_outputs, L, L)), np.empty((self.n_outputs, L, L))
-        ratio = 0.0
-        sub = np.ix_(ls, ls)
+        C_hat, dV_hat = (np.empty((self.n_outputs, L, L)), np.empty((self.n_outputs, L, L))) if estimates else (None, None)
         for n in range(self.n_outputs):
             centre = np.array([np.atleast_1d(np.asarray(self._pilot_sumse[n][i], dtype=np.float64)) for i in range(L)]) / N
             qfirst, qs1, qs2, rfirst, rs1, rs2 = field_pilot_moments(self._pilot_kept[n], ws[n], centre, differences=True)
             se_c[n], se_d[n] = field_pilot_standard_errors(N, qs1, qs2, rs1, rs2)
-            if tol is None:
-                continue
-            C_hat, dV_hat = qfirst + qs1 / N, rfirst + rs1 / N         # the means of q_s and r_s
-            var = np.diagonal(C_hat)
-            scale = np.sqrt(np.outer(var, var))
-            use = unknown[n][sub] & (scale > 0)
-            pairs = (no_dV[n] & self._coupling[n].linked)[sub] & np.triu(np.ones(scale.shape, dtype=bool), 1) & (dV_hat > 0) & (scale > 0)
-            for err, ref, mask in ((se_c[n], scale, use), (se_d[n], dV_hat, pairs)):
-                if mask.any():
-                    r = err[mask] / (tol * ref[mask])
-                    ratio = max(ratio, float(np.inf if np.isnan(r).any() else r.max()))
-        return se_c, se_d, ratio
-
-    # ---- what was measured --------------------------------------------------------------------------------------------------------
-    def _errors(self):
-        if self._pilot_errors is None:
-            why = self._no_field_moments() or "nothing was estimated from pilot samples (a problem loaded from a model-graph file?)"
-            raise BLUESTError("no standard errors of the pilot estimates: " + why)
-        return self._pilot_errors
-
-    get_covariance_errors = PilotErrorsMixin.get_covariance_errors
-    get_covariance_error = PilotErrorsMixin.get_covariance_error
-    get_mlmc_variance_errors = PilotErrorsMixin.get_mlmc_variance_errors
-    get_mlmc_variance_error = PilotErrorsMixin.get_mlmc_variance_error
+            if estimates:
+                C_hat[n], dV_hat[n] = qfirst + qs1 / N, rfirst + rs1 / N
+        return se_c, se_d, C_hat, dV_hat

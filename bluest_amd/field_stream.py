@@ -34,7 +34,7 @@ import numpy as np
 
 from . import _lib, fields
 from .blue_models import BLUEST_MAX_MODELS
-from .estimator import SLAB_BYTES
+from .estimator import SLAB_BYTES, sampled_columns
 from .field_errors import variance_of
 from .sap import BLUESTError
 
@@ -162,59 +162,26 @@ class StreamedFieldsMixin(object):
 
     # ---- whole estimators -------------------------------------------------------------------------------------------------------------
     def _sample_estimators(self, n_rep):
-        """FieldOutputsMixin._sample_estimators with the streamed groups never held: the same draws, the same flushes, the same
-        field_group_sums call per output and flush, where a streamed group stands as one row, its sums"""
-        out = self.MOSAP_output
-        samples = np.asarray(out["samples"])
-        chosen = np.flatnonzero(samples > 0)
-        groups = [out["flattened_groups"][g] for g in chosen]
-        ws, _ = self._field_weights()
-        widths = [len(w) for w in ws]
-        streamed = [self._field_streamed(samples[g], len(ls), widths) for ls, g in zip(groups, chosen)]
-        if not any(streamed):
-            return super()._sample_estimators(n_rep)
-        self._field_stream_refusals(covariances=True)
-        for ls in groups:
-            self._check_field_width(len(ls))
-        W = self._blue_weights()[0]
-        width = [len(ls) for ls in groups]
-        first_col = np.cumsum([0] + width[:-1]).tolist()
-        mus = [np.zeros((n_rep, d)) for d in widths]
+        """FieldOutputsMixin._sample_estimators: the same draws, the same flushes, the same field_group_sums call per output and
+        flush.  Where a group streams, what is refused is refused here, before anything is drawn or checked"""
+        widths = [len(w) for w in self._field_weights()[0]]
+        if any(self._field_streamed(m, len(ls), widths) for _, ls, _, m in sampled_columns(self.MOSAP_output)):
+            self._field_stream_refusals(covariances=True)
+        return super()._sample_estimators(n_rep)
+
+    def _field_group_values(self, col, widths):
+        """a streamed group is never held: it stands in the flush as one row, its sums, and a collecting solve() gets its
+        (N, variance of z) from the accumulators"""
+        g, ls, c, m = col
+        if not self._field_streamed(m, len(ls), widths):
+            return super()._field_group_values(col, widths)
         collecting = getattr(self, "_collecting_fields", None)
-        pending = []                    # (repeat, position of the group, per output [N, L, d_n] -- streamed: [1, L, d_n] --, streamed?)
-
-        def flush():
-            if not pending:
-                return
-            first, last = pending[0][0], pending[-1][0]
-            cols = np.concatenate([np.arange(first_col[gi], first_col[gi] + width[gi]) for _, gi, _, _ in pending])
-            where = [(r, int(chosen[gi])) for r, gi, _, _ in pending]
-            held = [i for i, p in enumerate(pending) if not p[3]]
-            for n in range(self.n_outputs):
-                segments = [p[2][n] for p in pending]
-                if held:                                                # the hooks of the bases see the held segments, as before
-                    self._field_segments_flushed([where[i] for i in held], n, [segments[i] for i in held])
-                _, part = fields.field_group_sums(segments, weights=W[n, cols], repeat_of=[r - first for r, _, _, _ in pending],
-                                                  R=last - first + 1)
-                mus[n][first:last + 1] += part
-            del pending[:]
-
-        held_bytes = 0
-        for r in range(n_rep):
-            for gi, (ls, g) in enumerate(zip(groups, chosen)):
-                m = int(samples[g])
-                if streamed[gi]:
-                    coefs = None if collecting is None else [W[n, first_col[gi]:first_col[gi] + width[gi]] for n in range(self.n_outputs)]
-                    got = stream_group(self, ls, m, widths, coefs)
-                    if collecting is not None:
-                        for n, (N, _, zsum, zsq) in enumerate(got):
-                            collecting[n][int(g)] = (N, variance_of(N, zsum, zsq))
-                    pending.append((r, gi, [s[1][None] for s in got], True))
-                else:
-                    pending.append((r, gi, fields.draw_field_values(self, ls, m, widths, device_ok=True), False))
-                held_bytes += m * len(ls) * sum(widths) * 8             # a streamed group counts as if it were held
-                if held_bytes >= fields.SLAB_BYTES:
-                    flush()
-                    held_bytes = 0
-        flush()
-        return mus
+        coefs = None
+        if collecting is not None:
+            W = self._blue_weights()[0]
+            coefs = [W[n, c:c + len(ls)] for n in range(self.n_outputs)]
+        got = stream_group(self, ls, m, widths, coefs)
+        if collecting is not None:
+            for n, (N, _, zsum, zsq) in enumerate(got):
+                collecting[n][g] = (N, variance_of(N, zsum, zsq))
+        return [s[1][None] for s in got], False

@@ -37,7 +37,7 @@ import numpy as np
 from . import _lib
 from ._blue_fn import _all_finite, _on_gpu
 from .blue_models import BLUEProblem, BLUEST_MAX_MODELS
-from .estimator import SLAB_BYTES, SamplingMixin
+from .estimator import SLAB_BYTES, SamplingMixin, flushed_draws, sampled_columns
 from .sap import BLUESTError
 
 BLUEST_FIELD_TILE = 8                # include/bluest_hip.h, Part 12
@@ -337,52 +337,52 @@ class FieldOutputsMixin(object):
         the group in the group list) of segments[i] [N, L, d_n] of output n, all ranks' shares joined.  A flush never splits a
         segment.  Nothing is done with them here; bluest_amd.field_errors.FieldErrorsMixin takes their weighted moments."""
 
+    def _sampled_moments_refused(self):
+        """no declared weights on the GPU path, so no moments of the drawn samples (FieldErrorsMixin, FieldCovariancesMixin; called
+        on the class, whatever the bases are): without SamplingMixin the parent's host flow draws the samples, and an inner product
+        written in Python is not a weight vector"""
+        return (not isinstance(self, SamplingMixin) or not isinstance(self, FieldOutputsMixin)
+                or type(self).get_models_inner_products is not FieldOutputsMixin.get_models_inner_products)
+
+    def _field_group_values(self, col, widths):
+        """the step of _sample_estimators that obtains one sampled group col = (g, models, first column, m_g) of one repeat: (per
+        output this rank's share of the m_g samples [share, L, d_n], True).  bluest_amd.field_stream.StreamedFieldsMixin returns a
+        large group's sums as one row [1, L, d_n] and False: not held, so no flush hook sees it"""
+        return draw_field_values(self, col[1], col[3], widths, device_ok=True), True
+
     def _sample_estimators(self, n_rep):
         """per output mus [n_rep, d_n] of n_rep independent estimators of the current allocation, drawn and flushed as
         SamplingMixin._sample_estimators does, with one field_group_sums call per output and flush"""
         comm = self.get_comm()
         rank = comm.Get_rank()
-        out = self.MOSAP_output
-        samples = np.asarray(out["samples"])
-        chosen = np.flatnonzero(samples > 0)
-        groups = [out["flattened_groups"][g] for g in chosen]
-        for ls in groups:
+        cols = sampled_columns(self.MOSAP_output)
+        for _, ls, _, _ in cols:
             self._check_field_width(len(ls))
         ws, _ = self._field_weights()
         widths = [len(w) for w in ws]
         W = self._blue_weights()[0] if rank == 0 else None
-        width = [len(ls) for ls in groups]
-        first_col = np.cumsum([0] + width[:-1]).tolist()
         mus = [np.zeros((n_rep, d)) for d in widths]
-        pending = []                                                    # (repeat, position of the group, this rank's values per output)
 
-        def flush():
-            if not pending:
-                return
-            comm_size = comm.Get_size()
-            shares = comm.gather([[v.cpu().numpy() if comm_size > 1 and hasattr(v, "data_ptr") else v for v in p[2]] for p in pending],
-                                 root=0)                                # [rank][segment][output]
-            if rank == 0:
-                first, last = pending[0][0], pending[-1][0]
-                # a flush may begin or end inside a repeat: every segment brings the weights of its own group
-                cols = np.concatenate([np.arange(first_col[gi], first_col[gi] + width[gi]) for _, gi, _ in pending])
-                where = [(r, int(chosen[gi])) for r, gi, _ in pending]
-                for n in range(self.n_outputs):
-                    joined = [_joined([share[i][n] for share in shares]) for i in range(len(pending))]
-                    self._field_segments_flushed(where, n, joined)
-                    _, part = field_group_sums(joined, weights=W[n, cols], repeat_of=[r - first for r, _, _ in pending], R=last - first + 1)
-                    mus[n][first:last + 1] += part
-            del pending[:]
+        def draw(col):
+            values, held = self._field_group_values(col, widths)
+            if comm.Get_size() > 1:
+                values = [v.cpu().numpy() if hasattr(v, "data_ptr") else v for v in values]
+            return (values, held), col[3] * len(col[1]) * sum(widths) * 8
 
-        held = 0
-        for r in range(n_rep):
-            for gi, (ls, g) in enumerate(zip(groups, chosen)):
-                pending.append((r, gi, draw_field_values(self, ls, int(samples[g]), widths, device_ok=True)))
-                held += int(samples[g]) * len(ls) * sum(widths) * 8
-                if held >= SLAB_BYTES:
-                    flush()
-                    held = 0
-        flush()
+        def flush(pending, shares):                                     # shares[rank][segment] = (the values per output, held?)
+            first, last = pending[0][0], pending[-1][0]
+            # every segment brings the weights of its own group
+            columns = np.concatenate([np.arange(c, c + len(ls)) for _, (_, ls, c, _) in pending])
+            held = [i for i, (_, kept) in enumerate(shares[0]) if kept]
+            where = [(pending[i][0], pending[i][1][0]) for i in held]
+            for n in range(self.n_outputs):
+                joined = [_joined([share[i][0][n] for share in shares]) for i in range(len(pending))]
+                if held:                                                # the hooks see the held segments only
+                    self._field_segments_flushed(where, n, [joined[i] for i in held])
+                _, part = field_group_sums(joined, weights=W[n, columns], repeat_of=[r - first for r, _ in pending], R=last - first + 1)
+                mus[n][first:last + 1] += part
+
+        flushed_draws(self, n_rep, cols, SLAB_BYTES, draw, flush)
         return comm.bcast(mus if rank == 0 else None, root=0)
 
     def solve(self, K=4, budget=None, eps=None, groups=None, multi_groups=None, solver=None, verbose=True, continuous_relaxation=False,

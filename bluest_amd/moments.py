@@ -41,7 +41,7 @@ import numpy as np
 
 from . import _lib
 from .blue_models import BLUEProblem
-from .estimator import SLAB_BYTES, _segment_table
+from .estimator import SLAB_BYTES, _segment_table, collecting_solve, sampled_errors
 from .sap import BLUESTError
 
 
@@ -68,17 +68,26 @@ def _triangle(L):
     return at
 
 
-def _unpacked(counts, sizes, first, second):
-    """the outputs of Part 13 ([n_out, T] and [n_out, P] over all segments) as a list of (N, first [n_out, L], second [n_out, L, L]).
-    The packed triangles become full matrices width by width, not segment by segment: a variance test's batch has thousands."""
+def _triangles_by_width(sizes):
+    """per width L among the segments' `sizes`: (L, the segments of that width, where their pairs lie in the packed triangles of
+    all segments, [segment, L, L]).  Indexing with it turns packed triangles into full symmetric matrices width by width, not
+    segment by segment: a variance test's batch has thousands."""
     sizes = sizes.astype(np.int64)
     tri = sizes * (sizes + 1) // 2
-    col0, pair0 = np.cumsum(sizes) - sizes, np.cumsum(tri) - tri
-    out = [None] * len(sizes)
-    counts = counts.tolist()
+    pair0 = np.cumsum(tri) - tri
     for L in set(sizes.tolist()):
         which = np.flatnonzero(sizes == L)
-        square = second[:, pair0[which][:, None, None] + _triangle(L)].transpose(1, 0, 2, 3)  # [segment, n_out, L, L]
+        yield L, which, pair0[which][:, None, None] + _triangle(L)
+
+
+def _unpacked(counts, sizes, first, second):
+    """the outputs of Part 13 ([n_out, T] and [n_out, P] over all segments) as a list of (N, first [n_out, L], second [n_out, L, L])"""
+    sizes = sizes.astype(np.int64)
+    col0 = np.cumsum(sizes) - sizes
+    out = [None] * len(sizes)
+    counts = counts.tolist()
+    for L, which, at in _triangles_by_width(sizes):
+        square = second[:, at].transpose(1, 0, 2, 3)                                            # [segment, n_out, L, L]
         cols = first[:, col0[which][:, None] + np.arange(L)].transpose(1, 0, 2)                 # [segment, n_out, L]
         for s, f, m in zip(which.tolist(), np.ascontiguousarray(cols), np.ascontiguousarray(square)):
             out[s] = (counts[s], f, m)
@@ -95,6 +104,24 @@ def covariance_of(N, first, second):
 def group_covariances(values, slab_bytes=SLAB_BYTES):
     """list over the segments of C^ [n_out, L, L] = (second - first first' / N) / (N - 1), NaN where N < 2"""
     return [covariance_of(N, first, second) for N, first, second in group_moments(values, slab_bytes=slab_bytes)]
+
+
+def pool_covariances(problem, sampled):
+    """(Cs, dof) of pooled_covariances() from sampled[n] = {group: (N, C^ [L, L])} of output n"""
+    groups = problem.MOSAP_output["flattened_groups"]
+    Cs, dofs = [], []
+    for n in range(problem.n_outputs):
+        acc, dof = np.zeros((problem.M, problem.M)), np.zeros((problem.M, problem.M))
+        for g, (N, C_hat) in sorted(sampled[n].items()):
+            if N >= 2:
+                ix = np.ix_(groups[g], groups[g])
+                acc[ix] += (N - 1) * C_hat
+                dof[ix] += N - 1
+        C = np.array(problem.get_covariance(n), dtype=np.float64)
+        C[dof > 0] = acc[dof > 0] / dof[dof > 0]
+        Cs.append(C)
+        dofs.append(dof)
+    return Cs, dofs
 
 
 class MomentsMixin(object):
@@ -120,13 +147,7 @@ class MomentsMixin(object):
                     optimization_solver_params=optimization_solver_params)
         if self._moments_refused():
             return super().solve(**args)
-        self._collecting = {}
-        try:
-            result = super().solve(**args)
-            moments = self._collecting
-        finally:
-            self._collecting = None
-        self.sample_moments = self.get_comm().bcast(moments if self.get_comm().Get_rank() == 0 else None, root=0)
+        result, self.sample_moments = collecting_solve(self, super().solve, "_collecting", {}, args)
         return result
 
     def _sampled(self):
@@ -140,44 +161,14 @@ class MomentsMixin(object):
         """[n_outputs]: sqrt(sum_g m_g w' C w) over the sampled groups g, w the BLUE weights of the group's columns and C the
         covariance of the group's samples (source="samples"; the model's block where the group was drawn once) or the model's
         block throughout (source="model": sqrt(Vs) of solve() again)"""
-        if source not in ("samples", "model"):
-            raise ValueError("source must be 'samples' or 'model'")
-        moments = self._sampled()
-        comm = self.get_comm()
-        errs = None
-        if comm.Get_rank() == 0:
-            out = self.MOSAP_output
-            samples = np.asarray(out["samples"])
-            W = self._blue_weights()[0]
-            var, c = np.zeros(self.n_outputs), 0
-            for g in np.flatnonzero(samples > 0).tolist():
-                ls = np.asarray(out["flattened_groups"][g], dtype=np.int64)
-                N, C_hat = moments[g]
-                for n in range(self.n_outputs):
-                    w = W[n, c:c + len(ls)]
-                    if not w.any():                                     # the group is not in this output's mapping
-                        continue
-                    C = C_hat[n] if source == "samples" and N >= 2 else self.get_covariance(n)[np.ix_(ls, ls)]
-                    var[n] += samples[g] * (w @ C @ w)
-                c += len(ls)
-            errs = np.sqrt(var)
-        return comm.bcast(errs, root=0)
+        def share(moments, n, g, ls, w):
+            N, C_hat = moments[g]
+            C = C_hat[n] if source == "samples" and N >= 2 else self.get_covariance(n)[np.ix_(ls, ls)]
+            return w @ C @ w
+        return sampled_errors(self, source, self._sampled, share, promised=False)
 
     def pooled_covariances(self):
         """(Cs, dof), per output M x M: dof[i, j] = sum of N_g - 1 over the sampled groups with N_g >= 2 that hold both i and j,
         Cs[i, j] = sum (N_g - 1) C^_g[i, j] / dof[i, j] where dof > 0, elsewhere the entry of get_covariance(n) (NaN included)"""
         moments = self._sampled()
-        groups = self.MOSAP_output["flattened_groups"]
-        Cs, dofs = [], []
-        for n in range(self.n_outputs):
-            acc, dof = np.zeros((self.M, self.M)), np.zeros((self.M, self.M))
-            for g, (N, C_hat) in sorted(moments.items()):
-                if N >= 2:
-                    ix = np.ix_(groups[g], groups[g])
-                    acc[ix] += (N - 1) * C_hat[n]
-                    dof[ix] += N - 1
-            C = np.array(self.get_covariance(n), dtype=np.float64)
-            C[dof > 0] = acc[dof > 0] / dof[dof > 0]
-            Cs.append(C)
-            dofs.append(dof)
-        return Cs, dofs
+        return pool_covariances(self, [{g: (N, C_hat[n]) for g, (N, C_hat) in moments.items()} for n in range(self.n_outputs)])

@@ -154,11 +154,37 @@ def next_pilot_size(N, r, size, N_max):
     return min(N_max, next_divisible_number(max(N + size, want), size))
 
 
-class PilotErrorsMixin(object):
+def tolerance_ratio(tol, se_c, se_d, C_hat, dV_hat, unknown, no_dV, linked):
+    """the largest ratio of an error to what the tolerance allows over the estimated coupled entries of one output: SE(C^_ij)
+    against tol sqrt(C^_ii C^_jj) where `unknown`, SE(dV^_ij) against tol dV^_ij at i < j where `no_dV` and `linked`; all [L, L].
+    inf where an error that counts is NaN, 0.0 where nothing counts"""
+    ratio = 0.0
+    var = np.diagonal(C_hat)
+    scale = np.sqrt(np.outer(var, var))
+    use = unknown & (scale > 0)
+    pairs = (no_dV & linked) & np.triu(np.ones(scale.shape, dtype=bool), 1) & (dV_hat > 0) & (scale > 0)
+    for err, ref, mask in ((se_c, scale, use), (se_d, dV_hat, pairs)):
+        if mask.any():
+            r = err[mask] / (tol * ref[mask])
+            ratio = max(ratio, float(np.inf if np.isnan(r).any() else r.max()))
+    return ratio
+
+
+class _GrowingPilot(object):
+    """what PilotErrorsMixin and bluest_amd.field_pilot_errors.FieldPilotErrorsMixin share: the refusals, the growth loop, the
+    errors it writes back, the report and the accessors.  A mix-in on top of it supplies
+        _pilot_needs                      what a tolerance needs, for the refusal's message
+        _pilot_unavailable()              why the GPU sums of the pilot are not there, or None
+        _pilot_caps(ls, N, size)          (the largest pilot size, which cap binds: "samples" or "bytes")
+        _pilot_round(ls, N, estimates)    rank 0: (SE(C^), SE(dV^), C^, dV^) [n_outputs, L, L] of the values kept; the last two
+                                          only with `estimates`, else None
+        _pilot_reset()                    forget what the rounds kept (extend it for state of its own)
+        _pilot_reported(...)              the report (extend it for keys of its own)
+    and the hooks of its bases through which a round draws what is missing and rank 0 keeps what was drawn."""
     reorder_graph_nodes = reorder_all_graph_nodes = BLUEProblem._out_of_scope      # named here so that they refuse with a message
     pilot_report = None
     _pilot_errors = None                 # (errors of C [n_outputs, M, M], errors of dV [n_outputs, M, M])
-    _pilot_kept = None                   # rank 0, while the pilot runs: the values drawn so far [n_outputs, N, L]
+    _pilot_kept = None                   # rank 0, while the pilot runs: the values drawn so far
     _pilot_have = 0                      # every rank: how many samples the values kept on rank 0 hold
 
     def _pilot_tol(self):
@@ -167,20 +193,17 @@ class PilotErrorsMixin(object):
             raise ValueError("covariance_estimation_tol must be positive")
         return None if tol is None else float(tol)
 
-    def _no_pilot_sums(self):
-        """why the sums do not come from bluest_pilot_stats, or None"""
-        from .fields import FieldOutputsMixin
-        if isinstance(self, FieldOutputsMixin):
-            return "FieldOutputsMixin takes its sums from bluest_field_stats"
-        if type(self).get_models_inner_products is not BLUEProblem.get_models_inner_products:
-            return "inner products written in Python are summed on the host"
-        return None
+    def _pilot_reset(self):
+        self._pilot_kept, self._pilot_have = None, 0
+
+    def _pilot_reported(self, samples, rounds, ratio, converged, cap):
+        return dict(samples=samples, rounds=rounds, ratio=ratio, converged=converged)
 
     # ---- BLUEProblem's hooks ----------------------------------------------------------------------------------------------------
     def _init_inputs(self, C, costs):
-        why = self._no_pilot_sums()
+        why = self._pilot_unavailable()
         if why is not None and self._pilot_tol() is not None:
-            raise BLUESTError("covariance_estimation_tol needs the fourth moments of scalar pilot samples: " + why)
+            raise BLUESTError("covariance_estimation_tol needs %s: %s" % (self._pilot_needs, why))
         return super()._init_inputs(C, costs)
 
     def _init_from_datafile(self, datafile, costs):
@@ -188,20 +211,10 @@ class PilotErrorsMixin(object):
             raise BLUESTError("covariance_estimation_tol needs pilot samples: a problem loaded from a model-graph file draws none")
         return super()._init_from_datafile(datafile, costs)
 
-    # ---- PilotMixin's hooks: a round draws what is missing, rank 0 keeps what was drawn --------------------------------------------
-    def _pilot_values(self, ls, N):
-        return super()._pilot_values(ls, N - self._pilot_have)
-
-    def _pilot_gathered(self, ls, values):
-        if self._pilot_kept is not None:
-            values = np.concatenate([self._pilot_kept, values], axis=1)                   # round-major, then in rank order
-        self._pilot_kept = values
-        return values
-
     def estimate_missing_covariances(self, N):
-        """PilotMixin.estimate_missing_covariances, then the standard errors of what it estimated; with
+        """the bases' estimate_missing_covariances, then the standard errors of what it estimated; with
         params["covariance_estimation_tol"] the pilot grows from N samples until the errors meet the tolerance"""
-        if self._no_pilot_sums() is not None:
+        if self._pilot_unavailable() is not None:
             return super().estimate_missing_covariances(N)
         unknown = [cp.linked & np.isnan(cp.cov) for cp in self._coupling]
         ls = [int(l) for l in np.flatnonzero(np.logical_or.reduce(unknown).any(axis=1))]
@@ -209,13 +222,14 @@ class PilotErrorsMixin(object):
         nan = lambda: np.full((self.n_outputs, self.M, self.M), np.nan)
         if len(ls) == 0:                                                # nothing to estimate: nothing has an error
             if self._pilot_errors is None:
-                self._pilot_errors, self.pilot_report = (nan(), nan()), dict(samples=0, rounds=0, ratio=None, converged=True)
+                self._pilot_errors, self.pilot_report = (nan(), nan()), self._pilot_reported(0, 0, None, True, None)
             return
         self._pilot_errors = (nan(), nan())
         tol, comm = self._pilot_tol(), self.get_comm()
         size, N = comm.Get_size(), int(N)
-        N_max = max(N, int(self.params.get("covariance_estimation_max_samples", 64 * N)))
+        N_max, cap = self._pilot_caps(ls, N, size)
         before = ([cp.cov.copy() for cp in self._coupling], [np.array(d, dtype=np.float64) for d in self.dV])
+        sub = np.ix_(ls, ls)
         rounds = 0
         try:
             while True:
@@ -227,7 +241,11 @@ class PilotErrorsMixin(object):
                 self._pilot_have = N
                 found = None
                 if comm.Get_rank() == 0:
-                    found = self._pilot_round(ls, N, unknown, no_dV, tol)
+                    se_c, se_d, C_hat, dV_hat = self._pilot_round(ls, N, tol is not None)
+                    ratio = 0.0 if tol is None else max(
+                        tolerance_ratio(tol, se_c[n], se_d[n], C_hat[n], dV_hat[n], unknown[n][sub], no_dV[n][sub],
+                                        self._coupling[n].linked[sub]) for n in range(self.n_outputs))
+                    found = (se_c, se_d, ratio)
                 se_c, se_d, ratio = comm.bcast(found, root=0)
                 more = None
                 if comm.Get_rank() == 0:                                # rank 0 decides
@@ -237,7 +255,7 @@ class PilotErrorsMixin(object):
                     break
                 N = more
         finally:
-            self._pilot_kept, self._pilot_have = None, 0
+            self._pilot_reset()
         where = np.ix_(range(self.n_outputs), ls, ls)
         self._pilot_errors[0][where] = se_c
         self._pilot_errors[1][where] = se_d
@@ -245,36 +263,16 @@ class PilotErrorsMixin(object):
             self._pilot_errors[0][n][~unknown[n]] = np.nan              # given, not estimated
             self._pilot_errors[1][n][~(no_dV[n] & np.triu(np.ones((self.M, self.M), dtype=bool), 1))] = np.nan
         converged = tol is None or ratio <= 1
-        self.pilot_report = dict(samples=N, rounds=rounds, ratio=float(ratio) if tol is not None else None, converged=converged)
+        self.pilot_report = self._pilot_reported(N, rounds, float(ratio) if tol is not None else None, converged,
+                                                 None if converged else cap)
         if not converged and comm.Get_rank() == 0:
             print("WARNING! The pilot estimates miss covariance_estimation_tol = %g after %d samples (largest error / tolerance: "
-                  "%.3g). Raise covariance_estimation_max_samples." % (tol, N, ratio))
-
-    def _pilot_round(self, ls, N, unknown, no_dV, tol):
-        """rank 0: (SE(C^), SE(dV^)) [n_outputs, L, L] of the values kept, and the largest ratio of an error to what the tolerance
-        allows over the estimated coupled entries (0 without a tolerance)"""
-        _, first, s11, s21, s22, tpow = pilot_fourth_moments(self._pilot_kept, differences=True)
-        se_c, se_d = pilot_standard_errors(N, first, s11, s21, s22, tpow)
-        if tol is None:
-            return se_c, se_d, 0.0
-        C_hat, dV_hat = _central(N, first, s11), _difference_variance(N, tpow)
-        ratio = 0.0
-        sub = np.ix_(ls, ls)
-        for n in range(self.n_outputs):
-            var = np.diagonal(C_hat[n])
-            scale = np.sqrt(np.outer(var, var))
-            use = unknown[n][sub] & (scale > 0)
-            pairs = (no_dV[n] & self._coupling[n].linked)[sub] & np.triu(np.ones(scale.shape, dtype=bool), 1) & (dV_hat[n] > 0) & (scale > 0)
-            for err, ref, mask in ((se_c[n], scale, use), (se_d[n], dV_hat[n], pairs)):
-                if mask.any():
-                    r = err[mask] / (tol * ref[mask])
-                    ratio = max(ratio, float(np.inf if np.isnan(r).any() else r.max()))
-        return se_c, se_d, ratio
+                  "%.3g). Raise covariance_estimation_max_%s." % (tol, N, ratio, cap))
 
     # ---- what was measured --------------------------------------------------------------------------------------------------------
     def _errors(self):
         if self._pilot_errors is None:
-            why = self._no_pilot_sums() or "nothing was estimated from pilot samples (a problem loaded from a model-graph file?)"
+            why = self._pilot_unavailable() or "nothing was estimated from pilot samples (a problem loaded from a model-graph file?)"
             raise BLUESTError("no standard errors of the pilot estimates: " + why)
         return self._pilot_errors
 
@@ -293,3 +291,36 @@ class PilotErrorsMixin(object):
 
     def get_mlmc_variance_error(self, n=0):
         return self._errors()[1][n].copy()
+
+
+class PilotErrorsMixin(_GrowingPilot):
+    _pilot_needs = "the fourth moments of scalar pilot samples"
+
+    def _pilot_unavailable(self):
+        """why the sums do not come from bluest_pilot_stats, or None"""
+        from .fields import FieldOutputsMixin
+        if isinstance(self, FieldOutputsMixin):
+            return "FieldOutputsMixin takes its sums from bluest_field_stats"
+        if type(self).get_models_inner_products is not BLUEProblem.get_models_inner_products:
+            return "inner products written in Python are summed on the host"
+        return None
+
+    def _pilot_caps(self, ls, N, size):
+        return max(N, int(self.params.get("covariance_estimation_max_samples", 64 * N))), "samples"
+
+    # ---- PilotMixin's hooks: a round draws what is missing, rank 0 keeps what was drawn [n_outputs, N, L] --------------------------
+    def _pilot_values(self, ls, N):
+        return super()._pilot_values(ls, N - self._pilot_have)
+
+    def _pilot_gathered(self, ls, values):
+        if self._pilot_kept is not None:
+            values = np.concatenate([self._pilot_kept, values], axis=1)                   # round-major, then in rank order
+        self._pilot_kept = values
+        return values
+
+    def _pilot_round(self, ls, N, estimates):
+        _, first, s11, s21, s22, tpow = pilot_fourth_moments(self._pilot_kept, differences=True)
+        se_c, se_d = pilot_standard_errors(N, first, s11, s21, s22, tpow)
+        if not estimates:
+            return se_c, se_d, None, None
+        return se_c, se_d, _central(N, first, s11), _difference_variance(N, tpow)
